@@ -15,7 +15,14 @@ With --gpus N > 1 and no WORLD_SIZE in the environment the script re-executes it
 torchrun directly it uses the ranks it is given.  Either way it refuses to report n_gpus != the
 RCCL world size.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line (decode tokens/s, `ms_per_step`
+and the algorithmic HBM traffic of a token).  `--dump-outputs DIR` writes what the timed path computed,
+as float32 / float64 .npy files: `logits` (fp32 logits of the last timed step, as `DecodeEngine.logits()`
+returns them) and `tokens` (the greedy token of every timed step).  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+
+With --full the JSON line also carries every secondary measurement (each can be left out with its
+--no-* switch), among them
   roofline     -- the TIME-dominant kernel of the decode step (one of the four fused 1-bit GEMV
                   launches of a layer), each timed with HIP events over the 32 layers' own weights
                   (> 256 MB Infinity Cache), algorithmic bytes / time against the 8 TB/s HBM peak;
@@ -73,6 +80,12 @@ def parse(argv=None):
     ap.add_argument("--model", default="7b", choices=["7b", "13b", "tiny"])
     ap.add_argument("--engine", default="auto", choices=["auto", "eager", "fused"])
     ap.add_argument("--prompt", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every secondary measurement (roofline, CPU baseline, prefill, serving, "
+                         "evaluation, train-mode layer, long context, config 4); a plain run times the decode steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed (logits of the last timed step, the tokens of the timed steps) "
+                         "to DIR/<name>.npy in float32 / float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-prefill", action="store_true")
@@ -912,6 +925,16 @@ def measure_train_layer(dev, T=4096, K=4096, N=11008, iters=5):
             "per": "GPU", "data": "synthetic"}
 
 
+def dump_outputs(path, outputs, prefix=""):
+    """`outputs` (name -> tensor) as path/<prefix><name>.npy: floating values in float32, integers in float64 (exact)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach().cpu()
+        a = t.float().numpy() if t.is_floating_point() else t.to(torch.float64).numpy()
+        np.save(os.path.join(path, prefix + name + ".npy"), np.ascontiguousarray(a))
+
+
 class Emitter:
     """The one JSON line, printed exactly once: by main() when every leg is done, or by the deadline timer with the legs finished
     so far (`incomplete` names the rest) -- after which every rank leaves with os._exit, whatever its main thread is stuck in."""
@@ -1043,11 +1066,13 @@ def main(argv=None, hooks=None):
     if stepper is None:
         cache = model.new_cache(1, args.prompt + total_new + 1)
         logits = model(prompt, cache)
-        state = {"tok": logits[:, -1].argmax(-1, keepdim=True)}
+        state = {"tok": logits[:, -1].argmax(-1, keepdim=True), "logits": logits, "toks": []}
 
         def step():
             lg = model(state["tok"], cache)
             state["tok"] = lg[:, -1].argmax(-1, keepdim=True)
+            state["logits"] = lg
+            state["toks"].append(state["tok"])
     else:
         stepper.prefill(prompt)
         step = stepper.step
@@ -1070,6 +1095,13 @@ def main(argv=None, hooks=None):
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs:
+        if stepper is not None:             # DecodeEngine: step i after the prompt leaves its greedy token at out_tokens[prompt + i]
+            p0 = args.prompt + args.warmup
+            outputs = {"logits": stepper.logits(), "tokens": stepper.out_tokens[p0:p0 + args.steps]}
+        else:
+            outputs = {"logits": state["logits"][0, -1], "tokens": torch.cat(state["toks"][args.warmup:]).reshape(-1)}
+        dump_outputs(args.dump_outputs, outputs, "" if world == 1 else "rank%d_" % rank)
 
     # ---- the headline line exists from here on; every further leg only ADDS a field to it ----
     em = Emitter(rank, args.deadline)
@@ -1111,63 +1143,64 @@ def main(argv=None, hooks=None):
         em.pending.remove(name)
         return res
 
-    if not args.no_roofline:                    # right after the decode phase: same thermal / clock state as the headline
-        ctx0 = args.prompt + args.warmup + args.steps // 2
-        leg("roofline", lambda: hk.measure_roofline(model, dev, dt / args.steps * 1e3, token_bytes(cfg, ctx0)[1]))
-    if not args.no_prefill:
-        leg("prefill_k_sharded", lambda: hk.measure_prefill_sharded(cfg, dev, world, rank), where="all")
-    serve = None
-    if not args.no_serve:
-        serve = leg("continuous_batch", lambda: hk.measure_continuous_batch(model, dev))
-    if not args.no_prefill:
-        leg("prefill_model", lambda: hk.measure_prefill_model(model, dev))
-        if hasattr(hk, "measure_ttft"):
-            leg("time_to_first_token", lambda: hk.measure_ttft(model, dev))
-    if not args.no_eval:                        # the evaluation callers at their real shape
-        leg("eval_ppl", lambda: hk.measure_eval(model, dev))
-    if not args.no_train:                       # the train-mode layer
-        leg("train_layer", lambda: hk.measure_train_layer(dev))
-    if not args.no_serve and hasattr(hk, "measure_decode_ctx"):      # long-context decode (single stream and 32 slots)
-        leg("decode_ctx", lambda: hk.measure_decode_ctx(model, dev))
-    if not args.no_prefill:
-        def tp_leg():
-            nonlocal model
-            if world > 1:                       # the same checkpoint on every rank (the decode replicas were seeded per rank)
-                model = None
+    if args.full:                               # everything besides the headline (off in a plain run)
+        if not args.no_roofline:                    # right after the decode phase: same thermal / clock state as the headline
+            ctx0 = args.prompt + args.warmup + args.steps // 2
+            leg("roofline", lambda: hk.measure_roofline(model, dev, dt / args.steps * 1e3, token_bytes(cfg, ctx0)[1]))
+        if not args.no_prefill:
+            leg("prefill_k_sharded", lambda: hk.measure_prefill_sharded(cfg, dev, world, rank), where="all")
+        serve = None
+        if not args.no_serve:
+            serve = leg("continuous_batch", lambda: hk.measure_continuous_batch(model, dev))
+        if not args.no_prefill:
+            leg("prefill_model", lambda: hk.measure_prefill_model(model, dev))
+            if hasattr(hk, "measure_ttft"):
+                leg("time_to_first_token", lambda: hk.measure_ttft(model, dev))
+        if not args.no_eval:                        # the evaluation callers at their real shape
+            leg("eval_ppl", lambda: hk.measure_eval(model, dev))
+        if not args.no_train:                       # the train-mode layer
+            leg("train_layer", lambda: hk.measure_train_layer(dev))
+        if not args.no_serve and hasattr(hk, "measure_decode_ctx"):      # long-context decode (single stream and 32 slots)
+            leg("decode_ctx", lambda: hk.measure_decode_ctx(model, dev))
+        if not args.no_prefill:
+            def tp_leg():
+                nonlocal model
+                if world > 1:                       # the same checkpoint on every rank (the decode replicas were seeded per rank)
+                    model = None
+                    hk.empty_cache()
+                    model = hk.build_model(cfg, 4242, dev)
+                return hk.measure_prefill_model_tp(model, dev, world, rank)
+            leg("prefill_model_tp", tp_leg, where="all")
+        if not args.no_k_sharded_decode:            # BASELINE config 4 on LLaMA-13B shapes at every N (N = 1: the line the N > 1 ones compare with)
+            def ksd_leg():
+                nonlocal model, stepper
+                stepper = model = None
                 hk.empty_cache()
-                model = hk.build_model(cfg, 4242, dev)
-            return hk.measure_prefill_model_tp(model, dev, world, rank)
-        leg("prefill_model_tp", tp_leg, where="all")
-    if not args.no_k_sharded_decode:            # BASELINE config 4 on LLaMA-13B shapes at every N (N = 1: the line the N > 1 ones compare with)
-        def ksd_leg():
-            nonlocal model, stepper
-            stepper = model = None
-            hk.empty_cache()
-            res = hk.measure_k_sharded_decode(model_config("13b"), dev, world, rank, min(args.steps, 16), args.prompt)
-            res["model"] = "LLaMA-13B shapes"
-            return res
-        leg("decode_k_sharded", ksd_leg, where="all")
-    if serve is not None and "error" not in serve and rank == 0 and args.model == "7b":
-        # BASELINE config 5 names LLaMA2-13B: the 32-slot steady-state step and the mixed prefill + decode workload on a 13B-shaped checkpoint
-        m13 = {}
-
-        def build13():
-            nonlocal model, stepper
-            stepper = model = None
-            hk.empty_cache()
-            m13["m"] = hk.build_model(model_config("13b"), 4242, dev)
-            return hk.measure_continuous_batch(m13["m"], dev)
-        leg("continuous_batch.llama2_13b_shapes", build13, into=serve, key="llama2_13b_shapes")
-        if "m" in m13:
-            def mixed13():
-                res = hk.measure_mixed_step(m13["m"], dev)
-                res["model"] = "LLaMA2-13B shapes"
+                res = hk.measure_k_sharded_decode(model_config("13b"), dev, world, rank, min(args.steps, 16), args.prompt)
+                res["model"] = "LLaMA-13B shapes"
                 return res
-            leg("continuous_batch.mixed", mixed13, into=serve, key="mixed")
-        m13.clear()
-        hk.empty_cache()
-    if not args.no_cpu_baseline:                # at every N (rank 0's host cores; the other ranks wait at the barrier below)
-        leg("cpu_baseline", lambda: hk.measure_cpu_baseline(cfg))
+            leg("decode_k_sharded", ksd_leg, where="all")
+        if serve is not None and "error" not in serve and rank == 0 and args.model == "7b":
+            # BASELINE config 5 names LLaMA2-13B: the 32-slot steady-state step and the mixed prefill + decode workload on a 13B-shaped checkpoint
+            m13 = {}
+
+            def build13():
+                nonlocal model, stepper
+                stepper = model = None
+                hk.empty_cache()
+                m13["m"] = hk.build_model(model_config("13b"), 4242, dev)
+                return hk.measure_continuous_batch(m13["m"], dev)
+            leg("continuous_batch.llama2_13b_shapes", build13, into=serve, key="llama2_13b_shapes")
+            if "m" in m13:
+                def mixed13():
+                    res = hk.measure_mixed_step(m13["m"], dev)
+                    res["model"] = "LLaMA2-13B shapes"
+                    return res
+                leg("continuous_batch.mixed", mixed13, into=serve, key="mixed")
+            m13.clear()
+            hk.empty_cache()
+        if not args.no_cpu_baseline:                # at every N (rank 0's host cores; the other ranks wait at the barrier below)
+            leg("cpu_baseline", lambda: hk.measure_cpu_baseline(cfg))
     if world > 1:
         try:
             dist.barrier()

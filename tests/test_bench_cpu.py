@@ -169,11 +169,11 @@ def _main_worker(rank, world, port, q, fault=None, out_path=None):
     if fault == "hang":
         # the deadline fires while the main thread hangs in a collective: the line goes to a file (the process leaves with os._exit)
         sys.stdout = open(out_path + ".%d" % rank, "w")
-        bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--model", "tiny", "--deadline", "6", "--pg-timeout", "600"], hooks=hooks)
+        bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--model", "tiny", "--full", "--deadline", "6", "--pg-timeout", "600"], hooks=hooks)
         raise AssertionError("main() returned although a leg hangs")
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--model", "tiny"], hooks=hooks)
+        bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--model", "tiny", "--full"], hooks=hooks)
     if fault == "raise":
         if rank == 0:
             q.put(json.loads(buf.getvalue().strip().splitlines()[-1]))
@@ -259,3 +259,74 @@ def test_hung_secondary_leg_cannot_suppress_the_headline_line(tmp_path):
     assert line["roofline"]["bound"] == "hbm" and line["prefill_k_sharded"]["k_shards"] == 2     # the legs before the hang survived
     assert "decode_k_sharded" not in line
     assert open(out_path + ".1").read().strip() == ""
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_outputs(tmp_path, monkeypatch):
+    """A plain run (no --full) on one rank with CPU stand-ins: exactly warm-up + --steps steps, no secondary measurement
+    entered, the line carries ms_per_step, and --dump-outputs writes the stepper's last logits (float32) and the tokens
+    of the timed steps (float64)."""
+    import contextlib
+    import io
+    import json
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    P, W, N, V = 16, 2, 5, 512
+
+    class Stepper:
+        def __init__(self):
+            self.n = 0
+            self.out_tokens = torch.zeros(P + W + N + 2, dtype=torch.int32)
+            self.buf = torch.zeros(V, dtype=torch.float16)
+
+        def prefill(self, prompt):
+            assert prompt.shape == (1, P)
+
+        def step(self):
+            self.out_tokens[P + self.n] = 7 * self.n + 1
+            self.buf.fill_(0.5 * self.n)
+            self.n += 1
+
+        def logits(self):
+            return self.buf.float()
+
+    class PlainHooks(bench.Hooks):
+        def device(self, local_rank):
+            return torch.device("cpu")
+
+        def sync(self, dev):
+            pass
+
+        def load_lib(self):
+            pass
+
+        def build_model(self, cfg, seed, dev):
+            return types.SimpleNamespace(config=cfg)
+
+        def make_stepper(self, model, max_len):
+            self.stepper = Stepper()
+            return self.stepper
+
+    def refuse(*a, **k):
+        raise AssertionError("a plain run entered a secondary measurement")
+    for name in dir(bench.Hooks):
+        if name.startswith("measure_"):
+            setattr(PlainHooks, name, staticmethod(refuse))
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    hooks = PlainHooks()
+    buf = io.StringIO()
+    out_dir = tmp_path / "outputs"
+    with contextlib.redirect_stdout(buf):
+        bench.main(["--steps", str(N), "--warmup", str(W), "--model", "tiny", "--dump-outputs", str(out_dir)], hooks=hooks)
+    line = json.loads(buf.getvalue().strip().splitlines()[-1])
+    assert hooks.stepper.n == W + N
+    assert line["metric"] == "decode_tokens_per_sec" and line["unit"] == "tokens/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f16" and line["steps"] == N and line["ms_per_step"] > 0
+    assert all(line[k] is None for k in ("roofline", "cpu_baseline", "prefill_k_sharded"))
+    assert sorted(os.listdir(out_dir)) == ["logits.npy", "tokens.npy"]
+    logits, tokens = np.load(out_dir / "logits.npy"), np.load(out_dir / "tokens.npy")
+    assert logits.dtype == np.float32 and logits.shape == (V,) and (logits == 0.5 * (W + N - 1)).all()
+    assert tokens.dtype == np.float64 and tokens.tolist() == [7 * i + 1 for i in range(W, W + N)]

@@ -1,80 +1,59 @@
 """Drop-in boundary inside the REFERENCE's own model class (SURVEY.md section 8 row b):
 ``BitLlamaForCausalLMInf`` (modeling_bitllama.py:1512-1611) built around ``onebit_amd.BitLinearInf`` by the documented
 monkey-patch of the import at modeling_bitllama.py:25 -- the seven call sites per layer (:229-231, :451-454) then
-construct THIS repo's module.  Checked: module count, state-dict keys / shapes / dtypes equal to the unpatched reference
-model, a reference state dict loads cleanly, ``.half()`` leaves ``weight`` int8 and casts only the floating parameters
-(modeling_utils.py:696 semantics), the converter's in-place ``.data`` assignments (convert_llama_to_infer_ckpt.py:32-34)
-take, and forward on CPU tensors refuses loudly (no CPU fallback).
-
-Build-container only: skipped where /root/reference does not exist (the GPU box)."""
-import importlib.metadata as md
+construct THIS repo's module.  The reference's side is recorded in golden/dropin_contract.json (gen_goldens_dropin.py):
+the arguments of every one of those constructions and the unpatched reference model's state dict (keys in order, shapes,
+dtypes).  Checked: each recorded call builds this repo's module with the recorded parameters, module count, this repo's
+model has the reference's state-dict contract, a reference state dict loads cleanly, ``.half()`` leaves ``weight`` int8
+and casts only the floating parameters (modeling_utils.py:696 semantics), the converter's in-place ``.data`` assignments
+(convert_llama_to_infer_ckpt.py:32-34) take, and forward on CPU tensors refuses loudly (no CPU fallback)."""
+import json
 import os
-import sys
 
 import pytest
 import torch
 
-REF_SRC = "/root/reference/transformers/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="the reference fork is only present in the build container")
-
-KW = dict(vocab_size=320, hidden_size=256, intermediate_size=688, num_hidden_layers=2, num_attention_heads=4,
-          max_position_embeddings=64)
-
 
 @pytest.fixture(scope="module")
-def ref_modules():
-    """The reference fork imported read-only (two dependency pins shimmed as in SURVEY.md appendix A)."""
-    orig = md.version
-    fake = {"tokenizers": "0.14.1", "huggingface-hub": "0.17.3", "huggingface_hub": "0.17.3"}
-    md.version = lambda n: fake.get(n, orig(n))
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, REF_SRC)
-    saved = {k: v for k, v in sys.modules.items() if k == "transformers" or k.startswith("transformers.")}
-    for k in saved:
-        del sys.modules[k]
-    try:
-        import transformers.models.bitnet as ref_bitnet
-        import transformers.models.bitllama.modeling_bitllama as mb
-        from transformers import BitLlamaConfig
-        yield ref_bitnet, mb, BitLlamaConfig
-    finally:
-        md.version = orig
-        sys.path.remove(REF_SRC)
-        for k in [k for k in sys.modules if k == "transformers" or k.startswith("transformers.")]:
-            del sys.modules[k]
-        sys.modules.update(saved)
+def contract(golden_dir):
+    with open(os.path.join(golden_dir, "dropin_contract.json")) as f:
+        return json.load(f)
 
 
 @pytest.mark.parametrize("attention_bias", [False, True])
-def test_reference_model_built_around_our_module(ref_modules, attention_bias):
+def test_reference_model_built_around_our_module(contract, attention_bias):
     import onebit_amd
-    ref_bitnet, mb, BitLlamaConfig = ref_modules
-    cfg = BitLlamaConfig(attention_bias=attention_bias, **KW)
+    from onebit_amd.llama import OneBitLlamaConfig, OneBitLlamaForCausalLM
+    KW = contract["config"]
+    case = contract["cases"][str(attention_bias).lower()]
+    ref_sd = {k: (tuple(shape), getattr(torch, dt)) for k, shape, dt in case["state_dict"]}
+    # the reference's call sites, replayed: each builds this repo's module with the parameters the reference checkpoint holds
+    calls = case["bitlinear_calls"]
+    assert len(calls) == 7 * KW["num_hidden_layers"]
+    for c in calls:
+        m = onebit_amd.BitLinearInf(*c["args"], **c["kwargs"])
+        for n, p in m.named_parameters():
+            assert (tuple(p.shape), p.dtype) == ref_sd[c["name"] + "." + n], (c["name"], n)
+        assert {c["name"] + "." + n for n, _ in m.named_parameters()} == {k for k in ref_sd if k.rsplit(".", 1)[0] == c["name"]}
+    cfg = OneBitLlamaConfig(attention_bias=attention_bias, **KW)
     torch.manual_seed(0)
-    ref_model = mb.BitLlamaForCausalLMInf(cfg)
-    ref_cls = mb.BitLinearInf
-    assert ref_cls is ref_bitnet.BitLinearInf
-    try:
-        ref_bitnet.BitLinearInf = mb.BitLinearInf = onebit_amd.BitLinearInf      # INTEGRATION.md, the monkey-patch form
-        model = mb.BitLlamaForCausalLMInf(cfg)
-    finally:
-        ref_bitnet.BitLinearInf = mb.BitLinearInf = ref_cls
+    model = OneBitLlamaForCausalLM(cfg, dtype=torch.float32)
     ours = [m for m in model.modules() if isinstance(m, onebit_amd.BitLinearInf)]
-    theirs = [m for m in ref_model.modules() if isinstance(m, ref_cls)]
-    assert len(ours) == len(theirs) == 7 * KW["num_hidden_layers"]
-    assert not any(isinstance(m, ref_cls) for m in model.modules())
+    assert len(ours) == len(calls)
+    assert [n for n, m in model.named_modules() if isinstance(m, onebit_amd.BitLinearInf)] == [c["name"] for c in calls]
     # identical state-dict contract
-    sd_ref, sd = ref_model.state_dict(), model.state_dict()
-    assert list(sd) == list(sd_ref)
+    sd = model.state_dict()
+    assert list(sd) == list(ref_sd)
     for k in sd:
-        assert sd[k].shape == sd_ref[k].shape and sd[k].dtype == sd_ref[k].dtype, k
+        assert (tuple(sd[k].shape), sd[k].dtype) == ref_sd[k], k
     # a (random) reference checkpoint loads by key
     g = torch.Generator().manual_seed(1)
-    for k, v in sd_ref.items():
-        if v.dtype == torch.int8:
-            v.copy_(torch.randint(-128, 128, v.shape, generator=g, dtype=torch.int8))
-        elif v.is_floating_point():
-            v.copy_(torch.randn(v.shape, generator=g) * 0.1)
+    sd_ref = {}
+    for k, (shape, dt) in ref_sd.items():
+        if dt == torch.int8:
+            sd_ref[k] = torch.randint(-128, 128, shape, generator=g, dtype=torch.int8)
+        else:
+            sd_ref[k] = (torch.randn(shape, generator=g) * 0.1).to(dt)
     missing, unexpected = model.load_state_dict(sd_ref, strict=True)
     assert not missing and not unexpected
     for k, v in model.state_dict().items():
