@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ONEBIT_ABI_VERSION 9
+#define ONEBIT_ABI_VERSION 10
 
 #define ONEBIT_F16 0
 #define ONEBIT_F32 1
@@ -408,6 +408,7 @@ typedef struct onebit_kshard_state {
 } onebit_kshard_state_t;
 int onebit_decode_step_ksharded(const onebit_model_t *model, const onebit_kshard_state_t *state, int32_t layer,
                                 int32_t segment, void *stream);
+/* (The K-sharded step stays greedy: it has no _sampled form.) */
 
 /* ABI 9: up to three projections that share their token rows' count T and in_features K (q | k | v, gate | up of a decoder layer), each on
  * ITS OWN pre-scaled rows a[i] = fp16(x * input_factor_i) [T, K] (onebit_rows_res_ln_rms with h_next), in ONE launch:
@@ -504,6 +505,45 @@ typedef struct onebit_mixed_state {
 /* max_dec_rows = state->n_slots of the steps that will use the workspace (the attention scratch is laid out for that many rows). */
 size_t onebit_mixed_workspace_bytes(const onebit_model_t *model, int64_t max_rows, int32_t max_dec_rows, int32_t attn_chunk);
 int onebit_mixed_step(const onebit_model_t *model, const onebit_mixed_state_t *state, void *stream);
+
+/* ---- sampled decoding (ABI 10): temperature, top-k, top-p and a Gumbel-max draw in place of the greedy argmax ----------------
+ * Per-row parameters live in DEVICE memory (a captured graph never needs re-capture when a request's parameters change), so the
+ * kernel takes every field value defensively:
+ *   do_sample == 0, temperature <= 0, NaN or +inf   greedy: the argmax kernels' token (first index on ties, only a value above
+ *                                                   -inf wins, NaN never; a row of only -inf / NaN gives 0)
+ *   top_k <= 0 or >= vocab                          top-k off
+ *   top_p >= 1 or NaN                               top-p off
+ * The draw for one fp16 logits row of length V and the index n of the generated token in its sequence:
+ *   s_i = float(logit_i) / temperature in fp32, NaN -> -inf; any s_i == +inf: the first such index; all -inf: 0
+ *   top-k keeps s_i >= the k-th largest s (ties at the threshold kept)
+ *   top-p: p = softmax(s) over the tokens top-k kept; token i stays iff the mass of kept tokens with a strictly larger score is
+ *          < top_p (the maximum always stays, ties stay together).  The masses are 40-bit fixed point, summed exactly.
+ *   token = argmax over the kept set of s_i + g_i (first index on ties), g_i = -log(-log(u_i)), u_i = ((r >> 8) + 0.5) * 2^-24,
+ *          r = word (i & 3) of Philox4x32-10 with key (seed_lo, seed_hi) and counter (n, stream, i >> 2, 0).
+ * The token is a pure function of (logits row, params, n): not of the batch size, the row index, the engine or the stream.
+ * n: the step's device-side position + 1 (decode: *pos + 1; batched: pos[b] + 1; mixed: row_pos[out_rows[r]] + 1): the first
+ * generated token of a prompt of S tokens has n = S.                                                                         */
+typedef struct onebit_sample_params {
+    int32_t do_sample;           /* 0: greedy row -- exactly the argmax kernels' token                                         */
+    float temperature;           /* > 0                                                                                        */
+    int32_t top_k;               /* 0 = off                                                                                    */
+    float top_p;                 /* >= 1 = off                                                                                 */
+    uint32_t seed_lo, seed_hi, stream, reserved;
+} onebit_sample_params_t;
+
+/* The standalone sampler: row r of logits (fp16, row stride ld >= vocab elements, or 0: every row reads the same row) drawn
+ * with params[r] at n = positions[r] into out_tokens[r].  All pointers device; 1 <= vocab <= 65536.                         */
+int onebit_sample_rows(const void *logits, int64_t ld, int32_t vocab, int32_t rows, const onebit_sample_params_t *params,
+                       const int32_t *positions, int32_t *out_tokens, void *stream);
+/* The decode steps with the final argmax launch replaced by the sampler (same launches otherwise, same outputs: decode
+ * *token / out_tokens[p] / *pos = p + 1; batched next_tokens[b], which with logits must be set; mixed next_tokens[r], logits
+ * required).  params: device [1] / [batch] / [n_out].  Argument errors are returned before any HIP call.                     */
+int onebit_decode_step_sampled(const onebit_model_t *model, const onebit_decode_state_t *state,
+                               const onebit_sample_params_t *params, void *stream);
+int onebit_decode_step_batched_sampled(const onebit_model_t *model, const onebit_batch_state_t *state,
+                                       const onebit_sample_params_t *params, void *stream);
+int onebit_mixed_step_sampled(const onebit_model_t *model, const onebit_mixed_state_t *state,
+                              const onebit_sample_params_t *params, void *stream);
 
 /* One fused decode GEMV launch (the building block of onebit_decode_step, exposed so that a
  * single kernel can be measured and tested in isolation): up to 3 projections sharing the input

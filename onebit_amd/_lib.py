@@ -19,7 +19,7 @@ FLAG_SKIP_LN = 1
 FLAG_Q_TOKEN_MAJOR = 2      # onebit_rows_qkv_rope
 FLAG_PRESCALED = 4
 FLAG_TILE_STATS = 8
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # name -> (restype, argtypes); must list every symbol include/onebit.h declares
 _i64, _vp, _int, _f, _u = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_uint
@@ -63,6 +63,11 @@ SYMBOLS = {
     "onebit_decode_step": (_int, [_vp, _vp, _vp]),      # (onebit_model_t*, onebit_decode_state_t*, stream)
     "onebit_decode_step_batched": (_int, [_vp, _vp, _vp]),   # (onebit_model_t*, onebit_batch_state_t*, stream)
     "onebit_decode_step_ksharded": (_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp]),   # (model*, onebit_kshard_state_t*, layer, segment, stream)
+    # ABI 10: sampled decoding (params: device onebit_sample_params_t rows)
+    "onebit_sample_rows": (_int, [_vp, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    "onebit_decode_step_sampled": (_int, [_vp, _vp, _vp, _vp]),            # (model*, onebit_decode_state_t*, params, stream)
+    "onebit_decode_step_batched_sampled": (_int, [_vp, _vp, _vp, _vp]),    # (model*, onebit_batch_state_t*, params, stream)
+    "onebit_mixed_step_sampled": (_int, [_vp, _vp, _vp, _vp]),             # (model*, onebit_mixed_state_t*, params, stream)
     "onebit_debug_fill_lds": (_int, [ctypes.c_uint32, _vp]),
     "onebit_fused_gemv": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
     "onebit_train_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64, _int]),

@@ -52,9 +52,22 @@ struct ObRowsNormCall {
     const float *z2, *z3;
 };
 OB_HIDDEN int ob_rows_norm(const ObRowsNormCall &c, hipStream_t s);
-// fp16 lm_head for B <= 64 rows + greedy token per row (ob_b_lmhead_kernel + ob_b_argmax_kernel)
+// One launch of the sampler (onebit_sample.hip, ob_sample.h): rows of fp16 logits -> a token per row under per-row
+// onebit_sample_params_t.  n of row r = pos[pos_rows ? pos_rows[r] : r] + pos_add.  Writes out[r], or in the single-stream
+// form (rows == 1, token != NULL) *token, out_tokens[p] (p < max_out) and *pos_w = p + 1, as ob_dec_argmax_kernel does.
+struct ObSampleCall {
+    const void *logits; int64_t ld; int V; int rows;
+    const onebit_sample_params_t *params;
+    const int32_t *pos, *pos_rows; int pos_add;
+    int32_t *out;
+    int32_t *token, *pos_w, *out_tokens; int max_out;
+};
+OB_HIDDEN int ob_sample_launch(const ObSampleCall &c, hipStream_t s);
+// fp16 lm_head for B <= 64 rows + greedy token per row (ob_b_lmhead_kernel + ob_b_argmax_kernel).  With `params` (device [B])
+// the token comes from the sampler instead of the argmax (logits required): n of row b = pos[pos_rows ? pos_rows[b] : b] + 1.
 OB_HIDDEN int ob_lm_head_argmax(const void *x, const void *lm_head, void *logits_or_null, float *part_val, int32_t *part_idx,
-                                int32_t *next_tokens, int B, int H, int V, hipStream_t s);
+                                int32_t *next_tokens, int B, int H, int V, hipStream_t s,
+                                const onebit_sample_params_t *params = nullptr, const int32_t *pos = nullptr, const int32_t *pos_rows = nullptr);
 // up to three projections that share T and K in ONE LDS-DMA skinny launch (2 <= T <= 64) on their pre-scaled rows a[i] [T, K]:
 // u[i] = fp16(fp16(W_i . a_i) * g_i).  Returns ONEBIT_E_SHAPE when a projection is not eligible (the caller falls back to
 // onebit_linear_forward per projection).

@@ -1491,7 +1491,10 @@ static ObChainCtx *ob_chain_ctx()
     return &c;
 }
 
-extern "C" int onebit_decode_step_batched(const onebit_model_t *m, const onebit_batch_state_t *st, void *stream)
+static int ob_batched_head(const onebit_model_t *m, const onebit_batch_state_t *st, const onebit_sample_params_t *params, hipStream_t s);
+
+// the batched step; params == NULL: greedy, else the sampler draws next_tokens (onebit_decode_step_batched_sampled)
+static int ob_decode_step_batched(const onebit_model_t *m, const onebit_batch_state_t *st, const onebit_sample_params_t *params, void *stream)
 {
     if (!m || !st) return ob_fail(ONEBIT_E_ARG, "decode_step_batched: null model/state");
     if (st->struct_size != sizeof(onebit_batch_state_t))
@@ -1561,15 +1564,30 @@ extern "C" int onebit_decode_step_batched(const onebit_model_t *m, const onebit_
         }
         if (!join_all()) return ob_launch_status("decode_step_batched(join)");
     }
-    return ob_batched_head(m, st, s);
+    return ob_batched_head(m, st, params, s);
+}
+
+extern "C" int onebit_decode_step_batched(const onebit_model_t *m, const onebit_batch_state_t *st, void *stream)
+{
+    return ob_decode_step_batched(m, st, nullptr, stream);
+}
+
+extern "C" int onebit_decode_step_batched_sampled(const onebit_model_t *m, const onebit_batch_state_t *st, const onebit_sample_params_t *params,
+                                                  void *stream)
+{
+    if (!m || !st || !params) return ob_fail(ONEBIT_E_ARG, "decode_step_batched_sampled: null model/state/params");
+    if (!st->next_tokens || !st->logits) return ob_fail(ONEBIT_E_ARG, "decode_step_batched_sampled: needs next_tokens and logits");
+    if (m->vocab < 1 || m->vocab > 65536) return ob_fail(ONEBIT_E_SHAPE, "decode_step_batched_sampled: vocab %d outside 1..65536", m->vocab);
+    return ob_decode_step_batched(m, st, params, stream);
 }
 
 int ob_lm_head_argmax(const void *x, const void *lm_head, void *logits, float *part_val, int32_t *part_idx, int32_t *next_tokens,
-                      int B, int H, int V, hipStream_t s)
+                      int B, int H, int V, hipStream_t s, const onebit_sample_params_t *params, const int32_t *pos, const int32_t *pos_rows)
 {
     int rc;
     if (B < 1 || B > 64) return ob_fail(ONEBIT_E_SHAPE, "lm_head: %d rows outside 1..64", B);
     if (H % 64 != 0) return ob_fail(ONEBIT_E_SHAPE, "lm_head needs hidden %% 64 == 0");
+    if (params && (!logits || !pos || V < 1 || V > 65536)) return ob_fail(ONEBIT_E_ARG, "lm_head: the sampler needs logits, positions and vocab 1..65536");
     ObBHeadArgs ha = {(const _Float16 *)x, (const _Float16 *)lm_head, (_Float16 *)logits, part_val, part_idx, B, H, V};
     const int hg = (V + OB_BH_ROWS - 1) / OB_BH_ROWS;
 #define OB_BH_GO(TT_)                                                                                              \
@@ -1584,17 +1602,24 @@ int ob_lm_head_argmax(const void *x, const void *lm_head, void *logits, float *p
     else OB_BH_GO(4);
 #undef OB_BH_GO
     if ((rc = ob_launch_status("lm_head"))) return rc;
+    if (params) {
+        ObSampleCall c = {};
+        c.logits = logits; c.ld = V; c.V = V; c.rows = B; c.params = params;
+        c.pos = pos; c.pos_rows = pos_rows; c.pos_add = 1; c.out = next_tokens;
+        return ob_sample_launch(c, s);
+    }
     hipLaunchKernelGGL(ob_b_argmax_kernel, dim3(B), dim3(256), 0, s, (const float *)part_val, (const int *)part_idx, hg, V, next_tokens);
     return ob_launch_status("lm_head(argmax)");
 }
 
-static int ob_batched_head(const onebit_model_t *m, const onebit_batch_state_t *st, hipStream_t s)
+static int ob_batched_head(const onebit_model_t *m, const onebit_batch_state_t *st, const onebit_sample_params_t *params, hipStream_t s)
 {
     if (!st->next_tokens) return 0;
     // batched lm_head + greedy sampling
     if (!m->lm_head || m->vocab <= 0 || !st->part_val || !st->part_idx)
         return ob_fail(ONEBIT_E_ARG, "decode_step_batched: next_tokens needs model->lm_head, vocab and the part_val / part_idx scratch");
-    return ob_lm_head_argmax(st->x, m->lm_head, st->logits, st->part_val, st->part_idx, st->next_tokens, st->batch, m->hidden, m->vocab, s);
+    return ob_lm_head_argmax(st->x, m->lm_head, st->logits, st->part_val, st->part_idx, st->next_tokens, st->batch, m->hidden, m->vocab, s,
+                             params, st->pos);
 }
 
 // ---- launchers the mixed step (onebit_mixed.hip) drives: ob_host.h ----
@@ -1785,7 +1810,8 @@ extern "C" int onebit_fused_gemv(const onebit_proj_t *projs, void *const *outs, 
     return ob_launch_dec_gemv(a, (hipStream_t)stream);
 }
 
-extern "C" int onebit_decode_step(const onebit_model_t *m, const onebit_decode_state_t *st, void *stream)
+// the decode step; params == NULL: greedy (ob_dec_argmax_kernel), else the sampler draws the token (onebit_decode_step_sampled)
+static int ob_decode_step(const onebit_model_t *m, const onebit_decode_state_t *st, const onebit_sample_params_t *params, void *stream)
 {
     if (!m || !st || !m->layers) return ob_fail(ONEBIT_E_ARG, "decode_step: null model/state");
     if (st->struct_size != sizeof(onebit_decode_state_t))
@@ -1961,9 +1987,28 @@ extern "C" int onebit_decode_step(const onebit_model_t *m, const onebit_decode_s
     const size_t head_lds = (size_t)H * 2 + 64 * 4 + 64 * 4;
     hipLaunchKernelGGL(ob_dec_lmhead_kernel, dim3(G), dim3(OB_DEC_THREADS), head_lds, s, hd);
     if ((rc = ob_launch_status("decode_step(lm_head)"))) return rc;
+    if (params) {
+        ObSampleCall c = {};
+        c.logits = st->logits; c.V = m->vocab; c.rows = 1; c.params = params;
+        c.pos = st->pos; c.pos_add = 1; c.token = st->token; c.pos_w = st->pos; c.out_tokens = st->out_tokens; c.max_out = st->max_out;
+        return ob_sample_launch(c, s);
+    }
     hipLaunchKernelGGL(ob_dec_argmax_kernel, dim3(1), dim3(256), 0, s, (const float *)st->part_val,
                        (const int *)st->part_idx, G, st->token, st->pos, st->out_tokens, st->max_out, m->vocab);
     return ob_launch_status("decode_step(argmax)");
+}
+
+extern "C" int onebit_decode_step(const onebit_model_t *m, const onebit_decode_state_t *st, void *stream)
+{
+    return ob_decode_step(m, st, nullptr, stream);
+}
+
+extern "C" int onebit_decode_step_sampled(const onebit_model_t *m, const onebit_decode_state_t *st, const onebit_sample_params_t *params,
+                                          void *stream)
+{
+    if (!params) return ob_fail(ONEBIT_E_ARG, "decode_step_sampled: null params");
+    if (m && (m->vocab < 1 || m->vocab > 65536)) return ob_fail(ONEBIT_E_SHAPE, "decode_step_sampled: vocab %d outside 1..65536", m->vocab);
+    return ob_decode_step(m, st, params, stream);
 }
 
 // ------------------------------------------------------------ K-sharded decode step (config 4) --

@@ -222,7 +222,8 @@ extern "C" size_t onebit_mixed_workspace_bytes(const onebit_model_t *m, int64_t 
     return ob_mixed_carve(m, max_rows, std::max<int32_t>(max_dec_rows, 1), OB_MIXED_MAX_SPLITS, nullptr).total;
 }
 
-extern "C" int onebit_mixed_step(const onebit_model_t *m, const onebit_mixed_state_t *st, void *stream)
+// the mixed step; params == NULL: greedy, else the sampler draws next_tokens (onebit_mixed_step_sampled)
+static int ob_mixed_step(const onebit_model_t *m, const onebit_mixed_state_t *st, const onebit_sample_params_t *params, void *stream)
 {
     if (!m || !st) return ob_fail(ONEBIT_E_ARG, "mixed_step: null model/state");
     if (st->struct_size != sizeof(onebit_mixed_state_t))
@@ -426,7 +427,22 @@ extern "C" int onebit_mixed_step(const onebit_model_t *m, const onebit_mixed_sta
         nf.x = w.xh; nf.rows = st->out_rows + o0; nf.T = no; nf.H = H; nf.rms_eps = m->rms_eps; nf.ln_eps = m->ln_eps;
         if ((rc = ob_rows_norm(nf, s))) return rc;
         void *lg = st->logits ? (void *)((_Float16 *)st->logits + (size_t)o0 * m->vocab) : nullptr;
-        if ((rc = ob_lm_head_argmax(w.xh, m->lm_head, lg, st->part_val, st->part_idx, st->next_tokens + o0, no, H, m->vocab, s))) return rc;
+        if ((rc = ob_lm_head_argmax(w.xh, m->lm_head, lg, st->part_val, st->part_idx, st->next_tokens + o0, no, H, m->vocab, s,
+                                    params ? params + o0 : nullptr, st->row_pos, st->out_rows + o0)))
+            return rc;
     }
     return 0;
+}
+
+extern "C" int onebit_mixed_step(const onebit_model_t *m, const onebit_mixed_state_t *st, void *stream)
+{
+    return ob_mixed_step(m, st, nullptr, stream);
+}
+
+extern "C" int onebit_mixed_step_sampled(const onebit_model_t *m, const onebit_mixed_state_t *st, const onebit_sample_params_t *params, void *stream)
+{
+    if (!m || !st || !params) return ob_fail(ONEBIT_E_ARG, "mixed_step_sampled: null model/state/params");
+    if (st->n_out > 0 && !st->logits) return ob_fail(ONEBIT_E_ARG, "mixed_step_sampled: needs logits");
+    if (m->vocab < 1 || m->vocab > 65536) return ob_fail(ONEBIT_E_SHAPE, "mixed_step_sampled: vocab %d outside 1..65536", m->vocab);
+    return ob_mixed_step(m, st, params, stream);
 }

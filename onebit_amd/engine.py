@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import copy
 import ctypes
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -96,6 +96,13 @@ class _FusedIn(ctypes.Structure):
 
 
 PRO_PLAIN, PRO_EMBED_RMS, PRO_RES_LN_RMS, PRO_SWIGLU = 0, 1, 2, 3
+
+
+def _check_params(params: torch.Tensor, rows: int, dev) -> None:
+    """Device rows of onebit_sample_params_t for a sampled step (sampling.pack)."""
+    if params.dtype != torch.uint8 or params.dim() != 2 or params.shape[0] < rows or params.shape[1] != 32 or \
+            not params.is_contiguous() or params.device != dev:
+        raise ValueError(f"sampling params must be contiguous uint8 [>= {rows}, 32] on {dev} (onebit_amd.sampling.pack)")
 
 
 def tile_stats_floats(n: int) -> int:
@@ -246,6 +253,12 @@ class DecodeEngine:
                              b["u_up"].data_ptr(), b["u_down"].data_ptr(), b["logits"].data_ptr(),
                              b["part_val"].data_ptr(), b["part_idx"].data_ptr(), 0, None, None, None, 0, 0, None)
         self._rope_cur = z(2 * D)
+        # sampled decoding: the armed request's onebit_sample_params_t row (device: the graphs read it at replay) and the
+        # sampled graph variants, captured on first use next to the greedy ones (which stay as they are)
+        self._params = torch.zeros(1, 32, dtype=torch.uint8, device=dev)
+        self._sampled = False
+        self._sgraphs = {}
+        self._use_graph = bool(use_graph)
         self._state.rope_cur = self._rope_cur.data_ptr()
         self.lib.onebit_decode_stats_floats.restype = ctypes.c_size_t
         self.lib.onebit_decode_stats_floats.argtypes = [ctypes.POINTER(_Model)]
@@ -346,6 +359,19 @@ class DecodeEngine:
                                              torch.cuda.current_stream(self.dev).cuda_stream)
         _lib.check(rc, "onebit_decode_step")
 
+    def _launch_sampled(self, st):
+        with torch.cuda.device(self.dev):
+            rc = self.lib.onebit_decode_step_sampled(ctypes.addressof(self._model), ctypes.addressof(st), self._params.data_ptr(),
+                                                     torch.cuda.current_stream(self.dev).cuda_stream)
+        _lib.check(rc, "onebit_decode_step_sampled")
+
+    def _arm(self, sampling) -> None:
+        """Greedy (None) or the given ``SamplingParams`` for the following steps."""
+        self._sampled = sampling is not None
+        if self._sampled:
+            from .sampling import pack
+            self._params.copy_(pack([sampling], self.dev))
+
     @torch.no_grad()
     def prefill(self, input_ids: torch.Tensor) -> torch.Tensor:
         """Run the prompt through the module path into the shared KV cache; returns the fp32 logits
@@ -356,6 +382,7 @@ class DecodeEngine:
         if S + 1 > self.max_len:
             raise ValueError("prompt longer than max_len")
         self.cache.length = 0
+        self._sampled = False
         logits = self.model(input_ids.to(self.dev), self.cache)
         self.token.copy_(logits[0, -1].argmax().to(torch.int32).reshape(1))
         self.pos.fill_(S)
@@ -365,11 +392,13 @@ class DecodeEngine:
         return logits
 
     @torch.no_grad()
-    def prime(self, input_ids: torch.Tensor) -> int:
+    def prime(self, input_ids: torch.Tensor, sampling=None) -> int:
         """The prompt into the KV cache through ``onebit_mixed_step`` (chunks of ``prefill_rows`` tokens, each ONE C call: GEMMs over
         all rows, ragged flash attention with past, lm_head + greedy token on the chunk's last row) and the engine armed with the
         first greedy token, which is returned.  Falls back to ``prefill`` when the native step does not take the model's shape
-        (head_dim other than 64 / 128)."""
+        (head_dim other than 64 / 128).
+        ``sampling`` (``onebit_amd.sampling.SamplingParams``): the first token and every later ``step`` are drawn by the sampler
+        (``onebit_mixed_step_sampled``, then the sampled decode graphs); None: greedy."""
         if input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("DecodeEngine is batch 1: input_ids must be [1, S]")
         S = input_ids.shape[1]
@@ -380,13 +409,19 @@ class DecodeEngine:
                 self._mixed = MixedStep(self.model, self.cache.layers, 1, self.max_len, max_rows=min(S, self._prefill_rows))
             except ValueError:
                 self._native_prefill = False
+        self._arm(sampling)
         if not self._native_prefill:
-            self.prefill(input_ids)
+            logits = self.prefill(input_ids)
+            self._arm(sampling)
+            if self._sampled:
+                from .sampling import sample_logits
+                self.token.copy_(sample_logits(logits[0, -1:].half(), self._params, [S]))
+                self.first_token = int(self.token.item())
             return self.first_token
         toks = input_ids[0].tolist()
         nxt = None
         for c0 in range(0, S, self._prefill_rows):
-            nxt = self._mixed.launch([(0, c0, toks[c0:c0 + self._prefill_rows])])
+            nxt = self._mixed.launch([(0, c0, toks[c0:c0 + self._prefill_rows])], params=self._params if self._sampled else None)
         self.cache.length = S
         self.token.copy_(nxt[:1])
         self.pos.fill_(S)
@@ -407,12 +442,31 @@ class DecodeEngine:
 
     def step(self):
         """Decode one token (asynchronous): consumes the device-side token, appends to the KV cache,
-        leaves the next greedy token on the device.  Raises when the KV cache is full: the kernels
-        index the cache, the rope tables and their score buffers by the device-side position."""
+        leaves the next greedy token on the device (sampled, n = position + 1, when ``prime`` armed a ``sampling``).  Raises when the
+        KV cache is full: the kernels index the cache, the rope tables and their score buffers by the device-side position."""
         if self._steps >= self.max_len:
             raise RuntimeError(f"DecodeEngine.step: KV cache full ({self.max_len} positions); build the engine with a larger max_len")
         long = bool(self._long_from) and (self._steps >= self._long_from or not self._short_ok)
         b64 = not long and self._steps < 64
+        if self._sampled:
+            if long and self._keyblock:
+                ns = self._kb_splits(self._steps + 1)
+                key, st = ("kb", ns), self._kb_states[ns][0]
+            else:
+                key = "long" if long else ("64" if b64 else "short")
+                st = self._state_long if long else (self._state64 if b64 else self._state)
+            g = self._sgraphs.get(key)
+            if g is not None:
+                g.replay()
+            else:
+                self._launch_sampled(st)                       # this step; the graph of its form is captured for the next ones
+                if self._use_graph:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self._launch_sampled(st)
+                    self._sgraphs[key] = g
+            self._steps += 1
+            return
         if long and self._keyblock:
             ns = self._kb_splits(self._steps + 1)                  # this step attends to positions 0 .. _steps
             g = self._kb_graphs.get(ns)
@@ -434,15 +488,17 @@ class DecodeEngine:
         return self.buf["logits"].float()
 
     @torch.no_grad()
-    def generate(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None) -> torch.Tensor:
+    def generate(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None, sampling=None) -> torch.Tensor:
         """Greedy decoding as the reference's ``greedy_search`` (generation/utils.py:2491-2540) for one
         sequence: the prompt followed by up to ``max_new_tokens`` tokens; with ``eos_token_id`` (int or
         list) the output ends with the first EOS token, as the reference's stopping criterion does
-        (the steps are enqueued without a host round trip, the cut is made afterwards)."""
+        (the steps are enqueued without a host round trip, the cut is made afterwards).  ``sampling``
+        (``onebit_amd.sampling.SamplingParams``): sampled decoding instead (token n of the sequence drawn at n, stream
+        ``sampling.stream``)."""
         S = input_ids.shape[1]
         if S + max_new_tokens > self.max_len:
             raise ValueError(f"generate: prompt {S} + max_new_tokens {max_new_tokens} exceeds the engine's max_len {self.max_len}")
-        self.prime(input_ids)
+        self.prime(input_ids, sampling=sampling)
         n = max_new_tokens - 1
         for _ in range(max(n, 0)):
             self.step()
@@ -542,15 +598,34 @@ class BatchedDecodeStep:
             self._state.qkv_stats = self._qkv_stats.data_ptr()
         self.lib.onebit_decode_step_batched.restype = ctypes.c_int
         self.lib.onebit_decode_step_batched.argtypes = [ctypes.POINTER(_Model), ctypes.POINTER(_BatchState), _vp]
+        self._state_s = None            # the sampled form's copy of the state (with logits), made on first use
 
-    def launch(self) -> torch.Tensor:
+    def _sampled_state(self):
+        if self._state_s is None:
+            if self.next_tokens is None:
+                raise ValueError("BatchedDecodeStep: the sampled step needs sample=True")
+            if self.logits is None:
+                self.logits = torch.zeros(self.batch, self.cfg.vocab_size, dtype=torch.float16, device=self.dev)
+            self._state_s = _BatchState.from_buffer_copy(self._state)
+            self._state_s.logits = self.logits.data_ptr()
+        return self._state_s
+
+    def launch(self, params: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Enqueue one step on the current stream; returns the final-norm output x [B, hidden]
         (a view of a persistent buffer).  With ``sample`` the greedy next token of every slot is in
-        ``self.next_tokens`` (int32 [B]) afterwards, computed by the same call."""
+        ``self.next_tokens`` (int32 [B]) afterwards, computed by the same call.  ``params``: device rows of
+        onebit_sample_params_t (``sampling.pack``, uint8 [B, 32]) -- the tokens are drawn by the sampler instead
+        (``onebit_decode_step_batched_sampled``, n = pos[b] + 1; needs ``sample``).  The sampled form writes the logits to
+        ``self.logits``, allocated on its first use without ``keep_logits`` (the greedy form keeps its own state)."""
         with torch.cuda.device(self.dev):
-            rc = self.lib.onebit_decode_step_batched(ctypes.byref(self._model), ctypes.byref(self._state),
-                                                     torch.cuda.current_stream(self.dev).cuda_stream)
-        _lib.check(rc, "onebit_decode_step_batched")
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            if params is None:
+                rc = self.lib.onebit_decode_step_batched(ctypes.byref(self._model), ctypes.byref(self._state), stream)
+            else:
+                _check_params(params, self.batch, self.dev)
+                rc = self.lib.onebit_decode_step_batched_sampled(ctypes.addressof(self._model), ctypes.addressof(self._sampled_state()),
+                                                                 params.data_ptr(), stream)
+        _lib.check(rc, "onebit_decode_step_batched" if params is None else "onebit_decode_step_batched_sampled")
         return self.buf["x"]
 
 
@@ -616,19 +691,22 @@ class MixedStep:
         self._rows = rows
         self._ensure_logits(ns)
 
-    def _ensure_logits(self, n: int):
-        if self.keep_logits and (self.logits is None or self.logits.shape[0] < n):
+    def _ensure_logits(self, n: int, need: bool = False):
+        if (self.keep_logits or need or self.logits is not None) and (self.logits is None or self.logits.shape[0] < n):
             self.logits = None
             self.logits = torch.zeros(max(n, self.n_slots), self.cfg.vocab_size, dtype=torch.float16, device=self.dev)
 
     @torch.no_grad()
-    def launch(self, items) -> torch.Tensor:
+    def launch(self, items, params: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Enqueue one step on the current stream.  ``items``: ``(slot, start, tokens)`` per scheduled request (distinct slots):
         ``tokens`` enter the request's cache slot at positions ``start ...``.  Returns the device tensor of greedy next tokens,
         one per item in the order given (the token after the item's LAST row: for a prompt chunk that is not the prompt's last one
         the caller ignores it).  An item may carry a fourth element ``k`` (default 1): lm_head runs on its last ``k`` rows (the
         evaluation caller scores a request's continuation rows) and the item contributes ``k`` consecutive entries to the returned
-        tokens and to ``logits``.  Asynchronous: synchronise before reading."""
+        tokens and to ``logits``.  Asynchronous: synchronise before reading.
+        ``params``: device rows of onebit_sample_params_t (``sampling.pack``, uint8 [n_out, 32], in the order of the returned
+        tokens): the tokens are drawn by the sampler (``onebit_mixed_step_sampled``, n = the row's position + 1; needs
+        logits: they go to ``self.logits``, allocated on first use)."""
         n_items = len(items)
         if n_items == 0 or n_items > self.n_slots:
             raise ValueError(f"MixedStep.launch: {n_items} items for {self.n_slots} slots")
@@ -646,7 +724,7 @@ class MixedStep:
         for i in range(1, n_items):
             out0[i] = out0[i - 1] + outs[i - 1]
         n_out = out0[-1] + outs[-1]
-        self._ensure_logits(n_out)
+        self._ensure_logits(n_out, need=params is not None)
         segs, row, n_dec, dec_ctx, seen = [], 0, 0, 0, set()
         for i in order:
             slot, start, toks = items[i][:3]
@@ -676,10 +754,16 @@ class MixedStep:
         base = d.data_ptr()
         state = _MixedState(ctypes.sizeof(_MixedState), T, n_dec, len(segs), n_out, ns, self.attn_chunk, dec_ctx,
                             base, base + 4 * R, base + 8 * R, seg_arr, base + 12 * R, self.next_tokens.data_ptr(),
-                            None if self.logits is None else self.logits.data_ptr(), self._part_val.data_ptr(), self._part_idx.data_ptr(),
+                            None if self.logits is None or not (self.keep_logits or params is not None) else self.logits.data_ptr(),
+                            self._part_val.data_ptr(), self._part_idx.data_ptr(),
                             self._ws.data_ptr() + self._ws_off, self._ws.numel() - self._ws_off)
         with torch.cuda.device(self.dev):
-            rc = self.lib.onebit_mixed_step(ctypes.byref(self._model), ctypes.byref(state), torch.cuda.current_stream(self.dev).cuda_stream)
-        _lib.check(rc, "onebit_mixed_step")
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            if params is None:
+                rc = self.lib.onebit_mixed_step(ctypes.byref(self._model), ctypes.byref(state), stream)
+            else:
+                _check_params(params, n_out, self.dev)
+                rc = self.lib.onebit_mixed_step_sampled(ctypes.byref(self._model), ctypes.byref(state), params.data_ptr(), stream)
+        _lib.check(rc, "onebit_mixed_step" if params is None else "onebit_mixed_step_sampled")
         self.launches += 1
         return self.next_tokens[:n_out]

@@ -434,13 +434,22 @@ class OneBitLlamaForCausalLM(nn.Module):
         return self.lm_head(h).float()
 
     @torch.no_grad()
-    def generate(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None, pad_token_id=None) -> torch.Tensor:
+    def generate(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None, pad_token_id=None, do_sample: bool = False,
+                 temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed=None) -> torch.Tensor:
         """Greedy search (generation/utils.py:2338, loop :2491-2540): argmax of the last position.
         With ``eos_token_id`` (int or list) a row that produced EOS is finished: its later tokens are
         ``pad_token_id`` (required then for B > 1, as in the reference, :2543-2546) and generation stops
         when every row is finished (:2562-2570).  Rows of ``input_ids`` must have equal length: there is
-        no attention_mask / left padding on this path (the reference's padded batches are not reproduced)."""
+        no attention_mask / left padding on this path (the reference's padded batches are not reproduced).
+        ``do_sample``: multinomial sampling through HF's warpers (``temperature``, ``top_k``, ``top_p``; generation/utils.py:811-840)
+        on the native sampler (``onebit_amd.sampling``): row b draws with ``seed`` (None: from torch's default generator) and
+        stream b, the token at sequence index n = ``cache.length``."""
         B, S = input_ids.shape
+        sp = None
+        if do_sample:
+            from .sampling import SamplingParams, pack
+            base = SamplingParams(temperature, top_k, top_p, seed)
+            sp = pack([base.with_stream(b) for b in range(B)], input_ids.device)
         cache = self.new_cache(B, S + max_new_tokens)
         eos = None
         if eos_token_id is not None:
@@ -454,7 +463,11 @@ class OneBitLlamaForCausalLM(nn.Module):
         logits = self.forward(input_ids, cache)
         out = [input_ids]
         for i in range(max_new_tokens):
-            nxt = logits[:, -1].argmax(-1, keepdim=True)
+            if sp is None:
+                nxt = logits[:, -1].argmax(-1, keepdim=True)
+            else:
+                from .sampling import sample_logits
+                nxt = sample_logits(logits[:, -1].half(), sp, [cache.length] * B).long().view(B, 1)
             if eos is not None:
                 nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
             out.append(nxt)
@@ -467,13 +480,16 @@ class OneBitLlamaForCausalLM(nn.Module):
         return torch.cat(out, dim=1)
 
 
-def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None, pad_token_id=None) -> torch.Tensor:
+def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None, pad_token_id=None, do_sample: bool = False,
+                     temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed=None) -> torch.Tensor:
     """``generate`` on the native engines, same return contract: B = 1 -> ``DecodeEngine`` (the prompt through ``onebit_mixed_step``,
     every further token one HIP-graph replay of ``onebit_decode_step``); B > 1 -> ``ContinuousBatcher`` with one slot per row (the
     prompts enter in ONE mixed step, decode-only steps replay the batched step's graph).  The steps are enqueued without looking at
     the tokens; EOS is applied afterwards exactly as ``generate`` applies it (a finished row continues with ``pad_token_id``, the
     output ends where every row is finished: generation/utils.py:2543-2570).  Engines are kept per (batch, max_len) on the model.
-    Greedy tokens equal ``generate``'s up to fp16 near-ties of the logits (the engines' kernels sum in another order)."""
+    Greedy tokens equal ``generate``'s up to fp16 near-ties of the logits (the engines' kernels sum in another order).
+    ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: as ``generate`` -- row b draws with the seed and stream b, token
+    n of the sequence at n -- so the sampled tokens equal ``generate``'s up to near-ties of the perturbed scores."""
     from .engine import DecodeEngine
     from .serving import ContinuousBatcher
     if input_ids.dim() != 2:
@@ -489,6 +505,10 @@ def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_tok
                 raise ValueError("generate: eos_token_id with batch > 1 needs pad_token_id (generation/utils.py:2543)")
             pad_token_id = next(iter(eos)) if not isinstance(eos_token_id, (list, tuple)) else int(eos_token_id[0])
     dev = self.lm_head.weight.device
+    sp = None
+    if do_sample:
+        from .sampling import SamplingParams
+        sp = SamplingParams(temperature, top_k, top_p, seed)
     engines = self.__dict__.setdefault("_native_engines", {})
     max_len = S + max_new_tokens
     key = (B, -(-max_len // 256) * 256)
@@ -502,14 +522,15 @@ def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_tok
             if len(engines) >= 4:
                 engines.clear()
             eng = engines[key] = DecodeEngine(self, max_len=key[1])
-        rows = [eng.generate(input_ids, max_new_tokens)[0, S:].tolist()]
+        rows = [eng.generate(input_ids, max_new_tokens, sampling=sp)[0, S:].tolist()]
     else:
         cb = engines.get(key)
         if cb is None:
             if len(engines) >= 4:
                 engines.clear()
             cb = engines[key] = ContinuousBatcher(self, max_batch=B, max_len=key[1])
-        ids = [cb.add_request(r, max_new_tokens) for r in input_ids.tolist()]
+        ids = [cb.add_request(r, max_new_tokens, sampling=None if sp is None else sp.with_stream(b))
+               for b, r in enumerate(input_ids.tolist())]
         out = cb.run()
         rows = [out[i] for i in ids]
         for i in ids:

@@ -41,6 +41,7 @@ class Request:
     t_add: float = 0.0                # wall clock (time.perf_counter): submitted / first token produced / finished
     t_first: float = 0.0
     t_done: float = 0.0
+    sampling: Optional[object] = None   # onebit_amd.sampling.SamplingParams; None: greedy
 
     @property
     def done(self) -> bool:
@@ -208,6 +209,14 @@ class ContinuousBatcher:
         self._g_pos_native = self._g_stage[2 * max_batch:]              # -1 = idle slot; converted to int32 inside the graph
         self._g_next = torch.zeros(max_batch, dtype=torch.long, device=self.dev)
         self._h_next = torch.zeros(max_batch, dtype=torch.long).pin_memory()
+        # sampled requests: a per-slot table of onebit_sample_params_t rows (a greedy slot has do_sample = 0), written from the
+        # scheduled requests and staged like _g_stage; a decode-only step with a sampled request replays the SAMPLED graph
+        # variant (captured on first use), an all-greedy step today's graph
+        self._h_params = torch.zeros(max_batch, 32, dtype=torch.uint8).pin_memory()
+        self._h_params_np = self._h_params.numpy()
+        self._g_params = torch.zeros(max_batch, 32, dtype=torch.uint8, device=self.dev)
+        self._graph_s = None
+        self._graph_fb_s = None
         # decode bursts: while the set of running requests cannot change (nothing to admit, nobody finishes), up to
         # `max_burst` steps are enqueued back to back -- each step's tokens feed the next ON THE DEVICE -- and the host
         # reads all of them after ONE synchronisation.  Same tokens as step-by-step execution.  OFF by default (max_burst = 1):
@@ -254,7 +263,7 @@ class ContinuousBatcher:
         from .engine import BatchedDecodeStep
         if splits not in self._long:
             self._long[splits] = [BatchedDecodeStep(self.model, self.cache, self.sched.max_batch, self.sched.max_len,
-                                                    attn_splits=splits, attn_chunk=self.attn_chunk), None]
+                                                    attn_splits=splits, attn_chunk=self.attn_chunk), None, None]     # greedy / sampled graph
         return self._long[splits][0]
 
     def _engine_for(self, ctx: int):
@@ -272,20 +281,50 @@ class ContinuousBatcher:
         except ValueError:
             return self._native, 0
 
+    def _stage_params(self, items: List[Item]) -> bool:
+        """Write the per-slot sampling rows of ``items``' requests (greedy rows elsewhere) and stage them stream-ordered;
+        True when a request of the step samples."""
+        sampled = [it for it in items if it.req.sampling is not None]
+        if not sampled:
+            return False
+        t = self._h_params_np
+        t[:] = 0
+        for it in sampled:
+            if getattr(it.req, "_sp_row", None) is None:
+                from .sampling import pack_host
+                it.req._sp_row = pack_host([it.req.sampling]).numpy()[0]
+            t[it.req.slot] = it.req._sp_row
+        self._g_params.copy_(self._h_params, non_blocking=True)          # stream-ordered before the replay / launch
+        return True
+
+    def _sample_rows(self, logits: torch.Tensor, items: List[Item]) -> List[int]:
+        """Tokens of the torch-glue path: greedy rows argmax of the fp32 logits, sampled rows the sampler on them (n = position
+        of the item's last row + 1)."""
+        from .sampling import sample_logits
+        out = logits.argmax(-1).tolist()
+        rows = [i for i, it in enumerate(items) if it.req.sampling is not None]
+        if rows:
+            tok = sample_logits(logits[rows].half(), [items[i].req.sampling for i in rows],
+                                [items[i].start + len(items[i].tokens) for i in rows]).tolist()
+            for i, t in zip(rows, tok):
+                out[i] = t
+        return out
+
     @torch.no_grad()
-    def _decode_static(self, eng=None):
+    def _decode_static(self, eng=None, sampled: bool = False):
         """One token for every slot (static shapes, no host-side shape dependence): the same
-        arithmetic as the batched decode branch of ``_forward`` with Lmax = max_len."""
+        arithmetic as the batched decode branch of ``_forward`` with Lmax = max_len.  ``sampled``: the tokens of the slots whose
+        row of the params table samples are drawn (n = position + 1)."""
         eng = eng if eng is not None else self._native
         if eng is not None:
             # idle slots keep pos = -1: their rows are computed, attention / cache append skipped
             eng.tokens.copy_(self._g_ids)
             eng.pos.copy_(self._g_pos_native)
-            x = eng.launch()
+            x = eng.launch(params=self._g_params if sampled and eng.next_tokens is not None else None)
             if eng.next_tokens is not None:                       # lm_head + argmax ran inside the C step
                 self._g_next.copy_(eng.next_tokens)
             else:
-                self._g_next.copy_((x @ self.model.lm_head.weight.t()).float().argmax(-1))
+                self._decode_tokens((x @ self.model.lm_head.weight.t()).float(), sampled)
             return
         cfg, m = self.cfg, self.model.model
         H, Hkv, D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
@@ -316,7 +355,15 @@ class ContinuousBatcher:
             o = torch.matmul(w, vals).reshape(B, H * D)
             h = h + att.o_proj(o)
             h = h + layer.mlp(layer.post_attention_layernorm(h))
-        self._g_next.copy_(self.model.lm_head(m.norm(h)).float().argmax(-1))
+        self._decode_tokens(self.model.lm_head(m.norm(h)).float(), sampled)
+
+    def _decode_tokens(self, logits: torch.Tensor, sampled: bool):
+        if not sampled:
+            self._g_next.copy_(logits.argmax(-1))
+            return
+        from .sampling import sample_logits
+        drawn = sample_logits(logits.half(), self._g_params, (self._g_pos + 1).to(torch.int32)).long()
+        self._g_next.copy_(torch.where(self._g_params[:, :4].any(1), drawn, logits.argmax(-1)))
 
     def _graph_step(self, items: List[Item], sync: bool = True) -> Optional[List[int]]:
         B = self.sched.max_batch
@@ -327,18 +374,22 @@ class ContinuousBatcher:
             sl = it.req.slot
             st[sl], st[B + sl], st[2 * B + sl] = it.tokens[0], it.start, it.start
         self._g_stage.copy_(self._h_stage, non_blocking=True)            # stream-ordered before the replay
+        sampled = self._last_sampled = self._stage_params(items)
         eng, key = self._engine_for(max(it.start for it in items) + 1)
-        graph = self._graph if key == 0 else self._long[key][1]
+        slot = 2 if sampled else 1
+        graph = (self._graph_s if sampled else self._graph) if key == 0 else self._long[key][slot]
         if graph is None:
-            self._decode_static(eng)                                # warm-up (allocations, lazy init): the step itself, idempotent
+            self._decode_static(eng, sampled)                       # warm-up (allocations, lazy init): the step itself, idempotent
             torch.cuda.synchronize(self.dev)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                self._decode_static(eng)
-            if key == 0:
+                self._decode_static(eng, sampled)
+            if key == 0 and sampled:
+                self._graph_s = graph
+            elif key == 0:
                 self._graph = graph
             else:
-                self._long[key][1] = graph
+                self._long[key][slot] = graph
         graph.replay()
         self.graph_steps += 1
         self.long_steps += key != 0
@@ -365,12 +416,13 @@ class ContinuousBatcher:
         return max(1, n)
 
     @torch.no_grad()
-    def _feedback_static(self):
-        """The step after a graph step of the SAME requests: token <- the token just produced, position + 1, on the device."""
+    def _feedback_static(self, sampled: bool = False):
+        """The step after a graph step of the SAME requests: token <- the token just produced, position + 1, on the device
+        (a sampled step's n follows from the position)."""
         nat = self._native
         nat.tokens.copy_(nat.next_tokens)
         nat.pos.add_((nat.pos >= 0).to(nat.pos.dtype))
-        nat.launch()
+        nat.launch(params=self._g_params if sampled else None)
         self._g_next.copy_(nat.next_tokens)
 
     def _graph_burst(self, items: List[Item], n: int) -> List[List[int]]:
@@ -378,22 +430,27 @@ class ContinuousBatcher:
         first = self._graph_step(items, sync=False)          # staged from the host; leaves its tokens in _g_next
         assert first is None
         self._g_ring[0].copy_(self._g_next, non_blocking=True)
-        if self._graph_fb is None:
+        sampled = self._last_sampled
+        if (self._graph_fb_s if sampled else self._graph_fb) is None:
             # the warm-up below runs one feedback step on the LIVE state and rewinds it: it writes KV row start + 1 of every
             # slot, which the replay rewrites identically -- provided that row exists and the burst does replay it
             assert n >= 2 and max(it.start for it in items) + 1 < self.sched.max_len, "burst warm-up outside the cache slot"
             tok0, pos0, nxt0 = self._native.tokens.clone(), self._native.pos.clone(), self._native.next_tokens.clone()
             torch.cuda.synchronize(self.dev)
-            self._feedback_static()                                  # warm-up on the live state ...
+            self._feedback_static(sampled)                           # warm-up on the live state ...
             torch.cuda.synchronize(self.dev)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._feedback_static()
-            self._graph_fb = g
+                self._feedback_static(sampled)
+            if sampled:
+                self._graph_fb_s = g
+            else:
+                self._graph_fb = g
             # ... then rewind it (the warm-up wrote one more KV row per slot: rewritten identically by the replay)
             self._native.tokens.copy_(tok0); self._native.pos.copy_(pos0); self._native.next_tokens.copy_(nxt0)
+        fb = self._graph_fb_s if sampled else self._graph_fb
         for j in range(1, n):
-            self._graph_fb.replay()
+            fb.replay()
             self._g_ring[j].copy_(self._g_next, non_blocking=True)
         self.graph_steps += n - 1
         self._h_ring[:n].copy_(self._g_ring[:n], non_blocking=True)
@@ -401,12 +458,23 @@ class ContinuousBatcher:
         rows = self._h_ring[:n].tolist()
         return [[row[it.req.slot] for it in items] for row in rows]
 
-    def add_request(self, prompt: List[int], max_new_tokens: int) -> int:
-        return self.sched.add(prompt, max_new_tokens)
+    def add_request(self, prompt: List[int], max_new_tokens: int, sampling=None) -> int:
+        """Queue a request; ``sampling`` (``onebit_amd.sampling.SamplingParams``): its tokens are drawn, token n of the sequence at
+        n with the request's seed and stream -- the same tokens whatever else is batched with it.  None: greedy."""
+        from .sampling import SamplingParams
+        if sampling is not None and not isinstance(sampling, SamplingParams):
+            raise TypeError("sampling must be an onebit_amd.sampling.SamplingParams or None")
+        rid = self.sched.add(prompt, max_new_tokens)
+        self.sched.waiting[-1].sampling = sampling
+        return rid
 
     def _mixed_step(self, items: List[Item]) -> List[int]:
-        """One step through ``onebit_mixed_step``: the greedy token after the last scheduled row of every item."""
-        nxt = self._mixed.launch([(it.req.slot, it.start, it.tokens) for it in items])
+        """One step through ``onebit_mixed_step``: the greedy (or sampled) token after the last scheduled row of every item."""
+        params = None
+        if any(it.req.sampling is not None for it in items):
+            from .sampling import pack
+            params = pack([it.req.sampling for it in items], self.dev)
+        nxt = self._mixed.launch([(it.req.slot, it.start, it.tokens) for it in items], params=params)
         self._h_mixed[:len(items)].copy_(nxt, non_blocking=True)
         torch.cuda.current_stream(self.dev).synchronize()                # the one host sync of the step
         self.mixed_steps += 1
@@ -510,7 +578,7 @@ class ContinuousBatcher:
         if self._mixed is not None:
             return self.sched.commit(items, self._mixed_step(items))
         logits = self._forward(items)
-        return self.sched.commit(items, logits.argmax(-1).tolist())
+        return self.sched.commit(items, self._sample_rows(logits, items))
 
     def run(self) -> Dict[int, List[int]]:
         """Drain the queue; {request id: generated tokens}."""
