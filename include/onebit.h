@@ -545,6 +545,61 @@ int onebit_decode_step_batched_sampled(const onebit_model_t *model, const onebit
 int onebit_mixed_step_sampled(const onebit_model_t *model, const onebit_mixed_state_t *state,
                               const onebit_sample_params_t *params, void *stream);
 
+/* ---- speculative decoding on the single-stream engine (prompt-lookup drafts; additive to ABI 10) ---------------------------
+ * One step runs k + 1 token rows of ONE cache slot -- the sequence's last token and k draft tokens, at positions p .. p + k --
+ * through the layer body of onebit_mixed_step (<= 64-row skinny GEMMs, ragged rope / append), attends with
+ * onebit_attention_decode_rows_mq, and takes lm_head + argmax (or the sampler, n = row_pos + 1) on ALL rows: chosen[i] is the
+ * token that follows row i.  The commit kernel then accepts the longest draft prefix with drafts[i] == chosen[i] and drafts the
+ * next step by prompt lookup, all on the device (graph-capture safe: nothing per step is read from the host):
+ *   n_emit = max(0, min(1 + |accepted prefix|, max_len - 1 - p, *remaining)),  n_acc = n_emit - 1
+ *   history[p + 1 .. p + n_emit] = chosen[0 .. n_emit - 1];  P = p + n_emit;  *pos = P;  *remaining -= n_emit
+ *   drafts: for n = ngram_max down to ngram_min (n <= P), the LATEST e in [n - 1, P - 1] with history[e - n + 1 .. e] ==
+ *           history[P - n + 1 .. P]; the first n with a match gives history[e + 1 .. min(e + k, P)] (n_drafted tokens);
+ *           the remaining draft slots repeat history[P] (the step's row count is fixed, they cost nothing extra)
+ *   tokens = [history[P], drafts], row_pos = [P .. P + k], record = {n_acc, P, n_drafted}
+ * Emitted tokens are exactly those of one-token-at-a-time decoding through the same step (greedy: the argmax of the verify
+ * pass's own logits; sampled: the sampler's draws, a pure function of (logits row, params, n)).  Rows whose keys were rejected
+ * are overwritten by the next step's rows before anything attends to them.  Rows at positions >= max_len are idle.          */
+typedef struct onebit_spec_state {
+    uint64_t struct_size;        /* sizeof(onebit_spec_state_t) as the caller compiled it (checked)                           */
+    int32_t k;                   /* draft tokens per step, 1 .. 15                                                            */
+    int32_t n_slots;             /* slots of the KV caches                                                                    */
+    int32_t attn_chunk;          /* positions per attention split, a multiple of 64                                           */
+    int32_t attn_splits;         /* 1 .. 64; attn_splits * attn_chunk should cover p + k + 1 (keys beyond are not attended)   */
+    int32_t ngram_max, ngram_min;/* 1 <= ngram_min <= ngram_max <= 16                                                         */
+    int32_t *tokens;             /* device [k + 1] in / out: the step's token rows                                            */
+    const int32_t *row_slot;     /* device [k + 1]: the sequence's cache slot, k + 1 times                                    */
+    int32_t *row_pos;            /* device [k + 1] in / out: p .. p + k                                                       */
+    int32_t *drafts;             /* device [k] in / out: tokens[1 ..] as the step verified them                               */
+    int32_t *chosen;             /* device [k + 1] out                                                                        */
+    int32_t *pos;                /* device [1] in / out: p, the position of the sequence's last token                         */
+    int32_t *remaining;          /* device [1] in / out: tokens still to emit                                                 */
+    int32_t *history;            /* device [max_len]: history[0 .. p] = the sequence so far (prompt + emitted tokens)         */
+    int32_t *record;             /* device [3] out: {n_acc, P, n_drafted}                                                     */
+    void *logits;                /* optional fp16 [k + 1, vocab] (required by the sampled form)                               */
+    float *part_val;             /* fp32 [ceil(vocab / 128) * 64] scratch                                                     */
+    int32_t *part_idx;           /* int32 [ceil(vocab / 128) * 64] scratch                                                    */
+    void *workspace;             /* onebit_spec_workspace_bytes(model, k, attn_chunk) bytes, 256-byte aligned, ZERO-FILLED ONCE */
+    size_t workspace_bytes;
+} onebit_spec_state_t;
+size_t onebit_spec_workspace_bytes(const onebit_model_t *model, int32_t k, int32_t attn_chunk);
+int onebit_spec_step(const onebit_model_t *model, const onebit_spec_state_t *state, void *stream);
+/* params: device [k + 1] (the request's row, k + 1 times) */
+int onebit_spec_step_sampled(const onebit_model_t *model, const onebit_spec_state_t *state,
+                             const onebit_sample_params_t *params, void *stream);
+/* The commit kernel alone (a caller with its own verify pass): reads k, ngram_*, tokens .. record of `state`; max_len <= 15360. */
+int onebit_spec_commit(const onebit_spec_state_t *state, int32_t max_len, void *stream);
+
+/* onebit_attention_decode_rows for q_per_seq (1 .. 16) CONSECUTIVE rows per sequence: rows s * q_per_seq + i, i = 0 .. q_per_seq - 1,
+ * are the queries of ONE sequence at positions p + i (slot and p read at the sequence's first row: row_slot / row_pos there), row i
+ * attending to keys 0 .. p + i.  One workgroup per (head, sequence, split) streams the split's keys / values once for all of them;
+ * each row's output is bit-identical to onebit_attention_decode_rows on that row alone.  Scratch as for `rows` single rows; a grid
+ * that does not cover the context attends to the chunk * n_splits keys it covers and still returns its tickets to zero.       */
+int onebit_attention_decode_rows_mq(const void *q, const void *k_cache, const void *v_cache, void *o, const void *h_next_or_null,
+                                    const int32_t *row_slot, const int32_t *row_pos, int64_t rows, int32_t q_per_seq, int32_t n_heads,
+                                    int32_t n_kv_heads, int32_t head_dim, int64_t n_slots, int64_t max_len, int32_t chunk,
+                                    int32_t n_splits, void *scratch, size_t scratch_bytes, void *stream);
+
 /* One fused decode GEMV launch (the building block of onebit_decode_step, exposed so that a
  * single kernel can be measured and tested in isolation): up to 3 projections sharing the input
  * vector x, each writing its pre-LayerNorm u = fp16(fp16(W.(h*x)) * g) to outs[i] (fp16 [N_i]).

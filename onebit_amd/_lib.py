@@ -68,6 +68,13 @@ SYMBOLS = {
     "onebit_decode_step_sampled": (_int, [_vp, _vp, _vp, _vp]),            # (model*, onebit_decode_state_t*, params, stream)
     "onebit_decode_step_batched_sampled": (_int, [_vp, _vp, _vp, _vp]),    # (model*, onebit_batch_state_t*, params, stream)
     "onebit_mixed_step_sampled": (_int, [_vp, _vp, _vp, _vp]),             # (model*, onebit_mixed_state_t*, params, stream)
+    # speculative decoding (additive to ABI 10)
+    "onebit_spec_workspace_bytes": (ctypes.c_size_t, [_vp, ctypes.c_int32, ctypes.c_int32]),
+    "onebit_spec_step": (_int, [_vp, _vp, _vp]),                           # (model*, onebit_spec_state_t*, stream)
+    "onebit_spec_step_sampled": (_int, [_vp, _vp, _vp, _vp]),              # (model*, onebit_spec_state_t*, params, stream)
+    "onebit_spec_commit": (_int, [_vp, ctypes.c_int32, _vp]),              # (onebit_spec_state_t*, max_len, stream)
+    "onebit_attention_decode_rows_mq": (_int, [_vp] * 7 + [_i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i64, _i64,
+                                                         ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
     "onebit_debug_fill_lds": (_int, [ctypes.c_uint32, _vp]),
     "onebit_fused_gemv": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
     "onebit_train_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64, _int]),

@@ -2,6 +2,8 @@
 // prefill + decode step of continuous batching (BASELINE config 5).
 //   onebit_attention_ragged        causal flash attention (ob_flash.h, RAGGED form) over prompt chunks of several sequences
 //   onebit_attention_decode_rows   split-KV decode attention (ob_fdec.h) for single-token rows, any context length
+//   onebit_attention_decode_rows_mq  the same for Q consecutive rows per sequence in one workgroup (ob_spec.h): K / V streamed once
+//   onebit_spec_step               one speculative decode step: the mixed step's layer body over k + 1 rows of one slot + the commit kernel
 //   onebit_mixed_step              one scheduler step: token rows of ALL scheduled items concatenated -> every 1-bit projection
 //                                  ONE GEMM over all rows, fused row glue, ragged attention, lm_head on the rows that sample
 // The reference has no counterpart for the batching itself; the arithmetic per row is modeling_bitllama.py:869-918 (layer),
@@ -15,6 +17,7 @@
 #include "ob_host.h"
 #include "ob_flash.h"
 #include "ob_fdec.h"
+#include "ob_spec.h"
 
 // ------------------------------------------------------------------------------------------------ grouped projections --
 extern "C" int onebit_linear_group_prescaled(const onebit_proj_t *projs, void *const *u, const void *const *a, int32_t n_proj, int64_t T, void *stream)
@@ -170,6 +173,55 @@ extern "C" int onebit_attention_decode_rows(const void *q, const void *k_cache, 
                           n_splits, scratch, (hipStream_t)stream);
 }
 
+// Q consecutive rows per sequence (rows = n_seq * q_per_seq): one workgroup per (head, sequence, split) serves them all (ob_spec.h).
+// The scratch is laid out as for `cap_rows` single rows (a sequence's ticket is its first row's word).
+template <int QT>
+static void ob_fdec_mq_launch_t(const ObFdecMqArgs &a, dim3 grid, hipStream_t stream)
+{
+    if (a.a.chunk % 128 == 0) hipLaunchKernelGGL((ob_fdec_mq_kernel<8, QT>), grid, dim3(OB_FD_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((ob_fdec_mq_kernel<4, QT>), grid, dim3(OB_FD_THREADS), 0, stream, a);
+}
+static int ob_fdec_mq_launch(const void *q, const void *k_cache, const void *v_cache, void *o, const void *h_next, const int32_t *row_slot,
+                             const int32_t *row_pos, int64_t rows, int32_t q_per_seq, int64_t cap_rows, int32_t n_heads, int32_t n_kv_heads,
+                             int32_t head_dim, int64_t n_slots, int64_t max_len, int32_t chunk, int32_t n_splits, void *scratch, hipStream_t stream)
+{
+    ObFdecMqArgs a = {};
+    a.a.q = (const _Float16 *)q; a.a.k = (const _Float16 *)k_cache; a.a.v = (const _Float16 *)v_cache; a.a.o = (_Float16 *)o;
+    a.a.h_next = (const _Float16 *)h_next; a.a.row_slot = row_slot; a.a.row_pos = row_pos;
+    a.a.H = n_heads; a.a.Hkv = n_kv_heads; a.a.D = head_dim; a.a.max_len = (int)max_len; a.a.n_slots = (int)n_slots; a.a.chunk = chunk; a.a.nsplit = n_splits;
+    a.a.inv_sqrt_d = 1.0f / sqrtf((float)head_dim);
+    a.Q = q_per_seq;
+    if (n_splits > 1) {
+        const size_t rh = (size_t)cap_rows * (size_t)n_heads;
+        char *p = (char *)scratch;
+        a.a.counter = (int *)p; p += ob_align256(rh * 4);
+        a.a.part_ml = (float *)p; p += ob_align256(rh * n_splits * 2 * 4);
+        a.a.part_o = (float *)p;
+    }
+    const dim3 grid((unsigned)n_heads, (unsigned)(rows / q_per_seq), (unsigned)n_splits);
+    if (q_per_seq <= 4) ob_fdec_mq_launch_t<4>(a, grid, stream);
+    else if (q_per_seq <= 8) ob_fdec_mq_launch_t<8>(a, grid, stream);
+    else ob_fdec_mq_launch_t<16>(a, grid, stream);
+    return ob_launch_status("attention_decode_rows_mq");
+}
+
+extern "C" int onebit_attention_decode_rows_mq(const void *q, const void *k_cache, const void *v_cache, void *o, const void *h_next,
+                                               const int32_t *row_slot, const int32_t *row_pos, int64_t rows, int32_t q_per_seq,
+                                               int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t n_slots, int64_t max_len,
+                                               int32_t chunk, int32_t n_splits, void *scratch, size_t scratch_bytes, void *stream)
+{
+    const int rc = ob_fdec_check("attention_decode_rows_mq", rows, n_heads, n_kv_heads, head_dim, n_slots, max_len, chunk, n_splits, scratch, scratch_bytes);
+    if (rc) return rc;
+    if (q_per_seq < 1 || q_per_seq > 16 || rows % q_per_seq != 0)
+        return ob_fail(ONEBIT_E_SHAPE, "attention_decode_rows_mq: %d rows per sequence (1 .. 16, dividing %lld rows)", q_per_seq, (long long)rows);
+    if (rows == 0) return 0;
+    if (!q || !k_cache || !v_cache || !o || !row_pos) return ob_fail(ONEBIT_E_ARG, "attention_decode_rows_mq: null pointer");
+    if (!ob_aligned(q, 16) || !ob_aligned(k_cache, 16) || !ob_aligned(v_cache, 16) || !ob_aligned(o, 2))
+        return ob_fail(ONEBIT_E_ALIGN, "attention_decode_rows_mq: q / k / v must be 16-byte aligned");
+    return ob_fdec_mq_launch(q, k_cache, v_cache, o, h_next, row_slot, row_pos, rows, q_per_seq, rows, n_heads, n_kv_heads, head_dim, n_slots, max_len,
+                             chunk, n_splits, scratch, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------- the mixed step --
 // Workspace: every [rows, *] activation of a step, carved from one caller buffer (256-byte aligned pieces).
 struct ObMixedWs {
@@ -223,7 +275,10 @@ extern "C" size_t onebit_mixed_workspace_bytes(const onebit_model_t *m, int64_t 
 }
 
 // the mixed step; params == NULL: greedy, else the sampler draws next_tokens (onebit_mixed_step_sampled)
-static int ob_mixed_step(const onebit_model_t *m, const onebit_mixed_state_t *st, const onebit_sample_params_t *params, void *stream)
+// spec_q > 0 (onebit_spec_step): the n_dec rows are spec_q consecutive positions of ONE slot -- their attention is the multi-query
+// launch with `spec_splits` splits, and out_rows may be NULL (every row samples, in order)
+static int ob_mixed_step(const onebit_model_t *m, const onebit_mixed_state_t *st, const onebit_sample_params_t *params, void *stream,
+                         int spec_q = 0, int spec_splits = 0)
 {
     if (!m || !st) return ob_fail(ONEBIT_E_ARG, "mixed_step: null model/state");
     if (st->struct_size != sizeof(onebit_mixed_state_t))
@@ -238,7 +293,7 @@ static int ob_mixed_step(const onebit_model_t *m, const onebit_mixed_state_t *st
     if (T < 0 || ND < 0 || NS < 0 || NO < 0 || ND > T || st->n_slots <= 0) return ob_fail(ONEBIT_E_ARG, "mixed_step: bad row counts");
     if (T == 0) return 0;
     if (!m->layers || !m->embed || !m->final_norm_w || !m->rope_cos || !m->rope_sin || !st->tokens || !st->row_slot || !st->row_pos ||
-        (NS > 0 && !st->segs) || (NO > 0 && (!st->out_rows || !st->next_tokens || !m->lm_head || !st->part_val || !st->part_idx)) || !st->workspace)
+        (NS > 0 && !st->segs) || (NO > 0 && ((!st->out_rows && !spec_q) || !st->next_tokens || !m->lm_head || !st->part_val || !st->part_idx)) || !st->workspace)
         return ob_fail(ONEBIT_E_ARG, "mixed_step: null pointer");
     // the prompt chunks' rows follow the decode rows and tile [n_dec, n_rows) without gaps, in order
     int64_t r = ND;
@@ -249,10 +304,10 @@ static int ob_mixed_step(const onebit_model_t *m, const onebit_mixed_state_t *st
     }
     if (r != T) return ob_fail(ONEBIT_E_SHAPE, "mixed_step: %d decode rows + the segments' rows = %lld, n_rows = %d", ND, (long long)r, T);
     const int chunk = st->attn_chunk > 0 ? st->attn_chunk : 256;
-    int nsplit = ob_mixed_splits(m, chunk, st->dec_ctx);
+    int nsplit = spec_q ? spec_splits : ob_mixed_splits(m, chunk, st->dec_ctx);
     if (nsplit > OB_MIXED_MAX_SPLITS) return ob_fail(ONEBIT_E_SHAPE, "mixed_step: %d attention splits (attn_chunk %d too small for this context)", nsplit, chunk);
     if (!ob_aligned(st->workspace, 256)) return ob_fail(ONEBIT_E_ALIGN, "mixed_step: workspace must be 256-byte aligned");
-    const ObMixedWs w = ob_mixed_carve(m, T, st->n_slots, nsplit, st->workspace);
+    const ObMixedWs w = ob_mixed_carve(m, T, spec_q ? spec_q : st->n_slots, nsplit, st->workspace);
     if (st->workspace_bytes < w.total) return ob_fail(ONEBIT_E_WSPACE, "mixed_step: workspace %zu < %zu bytes", st->workspace_bytes, w.total);
     hipStream_t s = (hipStream_t)stream;
     int rc;
@@ -384,7 +439,11 @@ static int ob_mixed_step(const onebit_model_t *m, const onebit_mixed_state_t *st
         if (NS > 0 && (rc = onebit_attention_ragged(w.q, L.k_cache, L.v_cache, w.attn, h_o, st->segs, NS, m->n_heads, m->n_kv_heads, D,
                                                     st->n_slots, m->max_len, s)))
             return rc;
-        if (ND > 0 && (rc = ob_fdec_launch(w.q, L.k_cache, L.v_cache, w.attn, h_o, st->row_slot, st->row_pos, ND, st->n_slots /* scratch rows */,
+        if (spec_q) {
+            if ((rc = ob_fdec_mq_launch(w.q, L.k_cache, L.v_cache, w.attn, h_o, st->row_slot, st->row_pos, ND, spec_q, ND, m->n_heads, m->n_kv_heads, D,
+                                        st->n_slots, m->max_len, chunk, nsplit, w.attn_scratch, s)))
+                return rc;
+        } else if (ND > 0 && (rc = ob_fdec_launch(w.q, L.k_cache, L.v_cache, w.attn, h_o, st->row_slot, st->row_pos, ND, st->n_slots /* scratch rows */,
                                            m->n_heads, m->n_kv_heads, D, st->n_slots, m->max_len, chunk, nsplit, w.attn_scratch, s)))
             return rc;
         // 5. o_proj
@@ -424,11 +483,11 @@ static int ob_mixed_step(const onebit_model_t *m, const onebit_mixed_state_t *st
         nf.hres_in = w.hA; nf.rms_w = m->final_norm_w;
         if (ks_prev) { nf.z0 = w.z[0]; nf.z1 = w.z[1]; nf.z2 = ks_prev > 2 ? w.z[2] : nullptr; nf.z3 = ks_prev > 3 ? w.z[3] : nullptr; nf.g_prev = m->layers[m->n_layers - 1].down.weight_scale; } else nf.u_prev = w.ud;
         nf.hres_out = w.hB;      // (hB rows 0 .. no - 1: scratch here)
-        nf.x = w.xh; nf.rows = st->out_rows + o0; nf.T = no; nf.H = H; nf.rms_eps = m->rms_eps; nf.ln_eps = m->ln_eps;
+        nf.x = w.xh; nf.rows = st->out_rows ? st->out_rows + o0 : nullptr; nf.T = no; nf.H = H; nf.rms_eps = m->rms_eps; nf.ln_eps = m->ln_eps;
         if ((rc = ob_rows_norm(nf, s))) return rc;
         void *lg = st->logits ? (void *)((_Float16 *)st->logits + (size_t)o0 * m->vocab) : nullptr;
         if ((rc = ob_lm_head_argmax(w.xh, m->lm_head, lg, st->part_val, st->part_idx, st->next_tokens + o0, no, H, m->vocab, s,
-                                    params ? params + o0 : nullptr, st->row_pos, st->out_rows + o0)))
+                                    params ? params + o0 : nullptr, st->row_pos, st->out_rows ? st->out_rows + o0 : nullptr)))
             return rc;
     }
     return 0;
@@ -445,4 +504,81 @@ extern "C" int onebit_mixed_step_sampled(const onebit_model_t *m, const onebit_m
     if (st->n_out > 0 && !st->logits) return ob_fail(ONEBIT_E_ARG, "mixed_step_sampled: needs logits");
     if (m->vocab < 1 || m->vocab > 65536) return ob_fail(ONEBIT_E_SHAPE, "mixed_step_sampled: vocab %d outside 1..65536", m->vocab);
     return ob_mixed_step(m, st, params, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ the speculative step --
+extern "C" size_t onebit_spec_workspace_bytes(const onebit_model_t *m, int32_t k, int32_t attn_chunk)
+{
+    if (k < 1 || k > 15) return 0;
+    return onebit_mixed_workspace_bytes(m, k + 1, k + 1, attn_chunk);
+}
+
+static int ob_spec_step(const onebit_model_t *m, const onebit_spec_state_t *st, const onebit_sample_params_t *params, void *stream)
+{
+    if (!m || !st) return ob_fail(ONEBIT_E_ARG, "spec_step: null model/state");
+    if (st->struct_size != sizeof(onebit_spec_state_t))
+        return ob_fail(ONEBIT_E_ARG, "spec_step: state struct_size %llu != %zu (caller built against another ABI: this library is ABI %d)",
+                       (unsigned long long)st->struct_size, sizeof(onebit_spec_state_t), ONEBIT_ABI_VERSION);
+    const int k = st->k;
+    if (k < 1 || k > 15) return ob_fail(ONEBIT_E_ARG, "spec_step: %d draft tokens per step (1 .. 15)", k);
+    if (st->n_slots <= 0) return ob_fail(ONEBIT_E_ARG, "spec_step: n_slots %d", st->n_slots);
+    if (st->attn_chunk < 64 || st->attn_chunk % 64 != 0 || st->attn_splits < 1 || st->attn_splits > OB_MIXED_MAX_SPLITS)
+        return ob_fail(ONEBIT_E_SHAPE, "spec_step: attn_chunk %d (a multiple of 64) x %d splits (1 .. %d)", st->attn_chunk, st->attn_splits, OB_MIXED_MAX_SPLITS);
+    if (st->ngram_min < 1 || st->ngram_max < st->ngram_min || st->ngram_max > 16)
+        return ob_fail(ONEBIT_E_ARG, "spec_step: n-gram lengths %d .. %d (1 <= min <= max <= 16)", st->ngram_min, st->ngram_max);
+    if (m->max_len <= 0 || m->max_len > OB_SPEC_MAX_LEN)
+        return ob_fail(ONEBIT_E_SHAPE, "spec_step: max_len %d outside 1 .. %d (the token history is searched in LDS)", m->max_len, OB_SPEC_MAX_LEN);
+    if (!st->tokens || !st->row_slot || !st->row_pos || !st->drafts || !st->chosen || !st->pos || !st->remaining || !st->history || !st->record ||
+        !st->part_val || !st->part_idx || !st->workspace)
+        return ob_fail(ONEBIT_E_ARG, "spec_step: null pointer");
+    if (params && !st->logits) return ob_fail(ONEBIT_E_ARG, "spec_step_sampled: needs logits");
+    const size_t need = onebit_spec_workspace_bytes(m, k, st->attn_chunk);
+    if (need == 0 || st->workspace_bytes < need) return ob_fail(ONEBIT_E_WSPACE, "spec_step: workspace %zu < %zu bytes for %d rows", st->workspace_bytes, need, k + 1);
+    onebit_mixed_state_t ms = {};
+    ms.struct_size = sizeof(ms);
+    ms.n_rows = ms.n_dec = ms.n_out = k + 1;
+    ms.n_slots = st->n_slots; ms.attn_chunk = st->attn_chunk;
+    ms.tokens = st->tokens; ms.row_slot = st->row_slot; ms.row_pos = st->row_pos;
+    ms.next_tokens = st->chosen; ms.logits = st->logits; ms.part_val = st->part_val; ms.part_idx = st->part_idx;
+    ms.workspace = st->workspace; ms.workspace_bytes = st->workspace_bytes;
+    int rc = ob_mixed_step(m, &ms, params, stream, k + 1, st->attn_splits);
+    if (rc) return rc;
+    ObSpecCommitArgs c = {};
+    c.chosen = st->chosen; c.drafts = st->drafts; c.tokens = st->tokens; c.row_pos = st->row_pos; c.pos = st->pos; c.remaining = st->remaining;
+    c.history = st->history; c.record = st->record; c.k = k; c.max_len = m->max_len; c.ngram_max = st->ngram_max; c.ngram_min = st->ngram_min;
+    static bool attr_set[OB_MAX_DEVICES] = {};
+    ob_set_max_lds_once(ob_spec_commit_kernel, attr_set, OB_SPEC_MAX_LEN * 4);
+    hipLaunchKernelGGL(ob_spec_commit_kernel, dim3(1), dim3(OB_SPEC_THREADS), (size_t)m->max_len * 4, (hipStream_t)stream, c);
+    return ob_launch_status("spec_commit");
+}
+
+extern "C" int onebit_spec_step(const onebit_model_t *m, const onebit_spec_state_t *st, void *stream)
+{
+    return ob_spec_step(m, st, nullptr, stream);
+}
+
+extern "C" int onebit_spec_step_sampled(const onebit_model_t *m, const onebit_spec_state_t *st, const onebit_sample_params_t *params, void *stream)
+{
+    if (!m || !st || !params) return ob_fail(ONEBIT_E_ARG, "spec_step_sampled: null model/state/params");
+    if (m->vocab < 1 || m->vocab > 65536) return ob_fail(ONEBIT_E_SHAPE, "spec_step_sampled: vocab %d outside 1..65536", m->vocab);
+    return ob_spec_step(m, st, params, stream);
+}
+
+// The commit kernel alone (tests, callers with their own verify pass): `state` as for onebit_spec_step; only k, ngram_*, the token
+// buffers, pos / remaining / history / record are read.
+extern "C" int onebit_spec_commit(const onebit_spec_state_t *st, int32_t max_len, void *stream)
+{
+    if (!st || st->struct_size != sizeof(onebit_spec_state_t)) return ob_fail(ONEBIT_E_ARG, "spec_commit: null state or foreign struct_size");
+    if (st->k < 1 || st->k > 15) return ob_fail(ONEBIT_E_ARG, "spec_commit: %d draft tokens per step (1 .. 15)", st->k);
+    if (st->ngram_min < 1 || st->ngram_max < st->ngram_min || st->ngram_max > 16) return ob_fail(ONEBIT_E_ARG, "spec_commit: n-gram lengths %d .. %d", st->ngram_min, st->ngram_max);
+    if (max_len <= 0 || max_len > OB_SPEC_MAX_LEN) return ob_fail(ONEBIT_E_SHAPE, "spec_commit: max_len %d outside 1 .. %d", max_len, OB_SPEC_MAX_LEN);
+    if (!st->tokens || !st->row_pos || !st->drafts || !st->chosen || !st->pos || !st->remaining || !st->history || !st->record)
+        return ob_fail(ONEBIT_E_ARG, "spec_commit: null pointer");
+    ObSpecCommitArgs c = {};
+    c.chosen = st->chosen; c.drafts = st->drafts; c.tokens = st->tokens; c.row_pos = st->row_pos; c.pos = st->pos; c.remaining = st->remaining;
+    c.history = st->history; c.record = st->record; c.k = st->k; c.max_len = max_len; c.ngram_max = st->ngram_max; c.ngram_min = st->ngram_min;
+    static bool attr_set[OB_MAX_DEVICES] = {};
+    ob_set_max_lds_once(ob_spec_commit_kernel, attr_set, OB_SPEC_MAX_LEN * 4);
+    hipLaunchKernelGGL(ob_spec_commit_kernel, dim3(1), dim3(OB_SPEC_THREADS), (size_t)max_len * 4, (hipStream_t)stream, c);
+    return ob_launch_status("spec_commit");
 }

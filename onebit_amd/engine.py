@@ -88,6 +88,14 @@ class _MixedState(ctypes.Structure):  # onebit_mixed_state_t (ABI 9)
                 ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t)]
 
 
+class _SpecState(ctypes.Structure):   # onebit_spec_state_t (additive to ABI 10)
+    _fields_ = [("struct_size", ctypes.c_uint64), ("k", _i32), ("n_slots", _i32), ("attn_chunk", _i32), ("attn_splits", _i32),
+                ("ngram_max", _i32), ("ngram_min", _i32),
+                ("tokens", _vp), ("row_slot", _vp), ("row_pos", _vp), ("drafts", _vp), ("chosen", _vp), ("pos", _vp),
+                ("remaining", _vp), ("history", _vp), ("record", _vp), ("logits", _vp), ("part_val", _vp), ("part_idx", _vp),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t)]
+
+
 class _FusedIn(ctypes.Structure):
     _fields_ = [("xin", _vp), ("embed", _vp), ("hres_in", _vp), ("u_prev", _vp), ("rms_w", _vp),
                 ("u_gate", _vp), ("u_up", _vp), ("token", _vp), ("hres_out", _vp),
@@ -488,16 +496,24 @@ class DecodeEngine:
         return self.buf["logits"].float()
 
     @torch.no_grad()
-    def generate(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None, sampling=None) -> torch.Tensor:
+    def generate(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None, sampling=None, speculative=None, drafts=None) -> torch.Tensor:
         """Greedy decoding as the reference's ``greedy_search`` (generation/utils.py:2491-2540) for one
         sequence: the prompt followed by up to ``max_new_tokens`` tokens; with ``eos_token_id`` (int or
         list) the output ends with the first EOS token, as the reference's stopping criterion does
         (the steps are enqueued without a host round trip, the cut is made afterwards).  ``sampling``
         (``onebit_amd.sampling.SamplingParams``): sampled decoding instead (token n of the sequence drawn at n, stream
-        ``sampling.stream``)."""
+        ``sampling.stream``).  ``speculative`` (``onebit_amd.speculative.SpecConfig``): after the prompt, every pass over the
+        weights verifies ``draft_tokens`` prompt-lookup drafts (``SpecStep``) and emits the confirmed ones plus one; the tokens
+        are the verify pass's own (argmax, or the sampler's draws), the per-step records ``(n_acc, pos, n_drafted)`` are kept in
+        ``self.spec_records``.  ``drafts`` (with ``speculative``): ``drafts(n) -> draft_tokens tokens`` proposed behind a sequence
+        of n tokens, in place of the device-side prompt lookup (a caller with a better guess; tests: oracle / adversarial)."""
         S = input_ids.shape[1]
         if S + max_new_tokens > self.max_len:
             raise ValueError(f"generate: prompt {S} + max_new_tokens {max_new_tokens} exceeds the engine's max_len {self.max_len}")
+        if speculative is not None:
+            return self._generate_speculative(input_ids, max_new_tokens, eos_token_id, sampling, speculative, drafts)
+        if drafts is not None:
+            raise ValueError("generate: drafts= needs speculative=")
         self.prime(input_ids, sampling=sampling)
         n = max_new_tokens - 1
         for _ in range(max(n, 0)):
@@ -506,6 +522,44 @@ class DecodeEngine:
         new: List[int] = [self.first_token] if max_new_tokens > 0 else []
         if n > 0:
             new += self.out_tokens[self._prompt_len:self._prompt_len + n].tolist()
+        if eos_token_id is not None:
+            eos = set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else {int(eos_token_id)}
+            for i, t in enumerate(new):
+                if t in eos:
+                    new = new[:i + 1]
+                    break
+        return torch.cat([input_ids.to(self.dev), torch.tensor([new], device=self.dev, dtype=input_ids.dtype)], dim=1)
+
+
+    def _generate_speculative(self, input_ids, max_new_tokens, eos_token_id, sampling, cfg, drafts_fn=None) -> torch.Tensor:
+        """``generate`` with speculative steps (``drafts_fn``: ``generate``'s ``drafts``)."""
+        S = input_ids.shape[1]
+        key = (int(cfg.draft_tokens), int(cfg.ngram_max), int(cfg.ngram_min))
+        steps = self.__dict__.setdefault("_spec_steps", {})
+        spec = steps.get(key)
+        if spec is None:
+            chunk = self._kb_chunk if self._keyblock else 64 * max(2, -(-self.max_len // (64 * 64)))
+            spec = steps[key] = SpecStep(self.model, self.cache.layers, 1, self.max_len, cfg, slot=0, attn_chunk=chunk,
+                                         use_graph=self._use_graph)
+        self.prime(input_ids, sampling=sampling)
+        self.spec_records = []
+        remaining = max_new_tokens - 1
+        if remaining > 0:
+            spec.arm(sampling)
+            spec.seed(input_ids[0].tolist() + [self.first_token], remaining)
+            pos = S
+            while remaining > 0:
+                spec.step(drafts=None if drafts_fn is None else drafts_fn(pos + 1))
+                n_acc, pos, n_drafted = spec.read_record()
+                self.spec_records.append((n_acc, pos, n_drafted))
+                if n_acc < 0:
+                    raise RuntimeError("speculative step emitted nothing (KV cache full)")
+                remaining -= n_acc + 1
+            new = spec.history[S:S + max_new_tokens].tolist()
+            self.cache.length = pos
+            self.set_state(new[-1], pos)
+        else:
+            new = [self.first_token] if max_new_tokens > 0 else []
         if eos_token_id is not None:
             eos = set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else {int(eos_token_id)}
             for i, t in enumerate(new):
@@ -767,3 +821,171 @@ class MixedStep:
         _lib.check(rc, "onebit_mixed_step" if params is None else "onebit_mixed_step_sampled")
         self.launches += 1
         return self.next_tokens[:n_out]
+
+
+class SpecStep:
+    """``onebit_spec_step`` bound to a model and ONE slot of its KV caches: a speculative decode step -- the sequence's last token
+    and ``k`` draft tokens as k + 1 rows through the mixed step's layer body, multi-query key-block attention
+    (``onebit_attention_decode_rows_mq``), lm_head + argmax (or the sampler) on every row, then the commit kernel: accept the
+    confirmed drafts, append the emitted tokens to ``history``, draft the next step by prompt lookup (``speculative.propose`` /
+    ``accept`` state the contract).  Everything a step reads is on the device; one HIP graph per (split count, greedy | sampled)
+    is captured on its second use.  The host reads the 12-byte commit record once per step (``read_record``) to pick the next
+    step's split count and to stop."""
+
+    def __init__(self, model: OneBitLlamaForCausalLM, caches, n_slots: int, max_len: int, cfg, slot: int = 0,
+                 attn_chunk: int = 128, keep_logits: bool = False, use_graph: bool = True):
+        mc = model.config
+        if not model.lm_head.weight.is_cuda:
+            raise RuntimeError("SpecStep needs the model on a ROCm GPU (no CPU fallback)")
+        model = fp16_view(model)
+        p = model.lm_head.weight
+        H, D = mc.hidden_size, mc.head_dim
+        if D not in (64, 128) or H % 64 != 0 or mc.num_attention_heads * D != H:
+            raise ValueError("SpecStep: head_dim must be 64 or 128 and hidden a multiple of 64")
+        if max_len > mc.max_position_embeddings:
+            raise ValueError("max_len exceeds max_position_embeddings (the rope tables have that many rows)")
+        if max_len > 15360:
+            raise ValueError("SpecStep: max_len above 15360 (the commit kernel searches the token history in LDS)")
+        if attn_chunk < 64 or attn_chunk % 64 or -(-max_len // attn_chunk) > 64:
+            raise ValueError("SpecStep: attn_chunk must be a multiple of 64 with at most 64 splits over max_len")
+        if not 0 <= slot < n_slots:
+            raise ValueError("SpecStep: slot outside the caches")
+        shape = (n_slots, mc.num_key_value_heads, max_len, D)
+        for i, (kc, vc) in enumerate(caches):
+            if tuple(kc.shape) != shape or tuple(vc.shape) != shape or not kc.is_contiguous() or not vc.is_contiguous() or \
+                    kc.dtype != torch.float16 or vc.dtype != torch.float16 or kc.device != p.device or vc.device != p.device:
+                raise ValueError(f"cache {i} must be contiguous float16 {shape} on {p.device}")
+        self.model, self.cfg, self.dev = model, mc, p.device
+        self.k, self.ngram_max, self.ngram_min = int(cfg.draft_tokens), int(cfg.ngram_max), int(cfg.ngram_min)
+        self.n_slots, self.max_len, self.slot, self.attn_chunk = int(n_slots), int(max_len), int(slot), int(attn_chunk)
+        self.lib = _lib.load()
+        self._model, self._keep = _model_struct(model, caches, max_len)
+        dev, k = self.dev, self.k
+        # one int32 block: tokens[16] | row_slot[16] | row_pos[16] | drafts[16] | chosen[16] | pos, remaining, -, - | record[4]
+        self._ints = torch.zeros(88, dtype=torch.int32, device=dev)
+        self._ints[16:32] = self.slot
+        self._h_ints = torch.zeros(88, dtype=torch.int32).pin_memory()
+        self._h_drafts = torch.zeros(16, dtype=torch.int32).pin_memory()
+        self.tokens, self.row_pos, self.drafts = self._ints[0:k + 1], self._ints[32:33 + k], self._ints[48:48 + k]
+        self.chosen, self.pos, self.remaining, self._rec_dev = self._ints[64:65 + k], self._ints[80:81], self._ints[81:82], self._ints[84:87]
+        self.history = torch.zeros(self.max_len, dtype=torch.int32, device=dev)
+        self._rec_host = torch.zeros(3, dtype=torch.int32).pin_memory()
+        nparts = -(-mc.vocab_size // 128) * 64
+        self._part_val = torch.zeros(nparts, dtype=torch.float32, device=dev)
+        self._part_idx = torch.zeros(nparts, dtype=torch.int32, device=dev)
+        self.keep_logits = bool(keep_logits)
+        self.logits = torch.zeros(k + 1, mc.vocab_size, dtype=torch.float16, device=dev)
+        self.lib.onebit_spec_workspace_bytes.argtypes = [ctypes.POINTER(_Model), _i32, _i32]
+        nb = int(self.lib.onebit_spec_workspace_bytes(ctypes.byref(self._model), k, self.attn_chunk))
+        if nb == 0:
+            raise ValueError("SpecStep: onebit_spec_workspace_bytes refused the model")
+        self._ws = torch.zeros(nb + 256, dtype=torch.uint8, device=dev)
+        self._ws_off = (-self._ws.data_ptr()) % 256
+        self._params = torch.zeros(k + 1, 32, dtype=torch.uint8, device=dev)
+        self._sampled = False
+        self._use_graph = bool(use_graph)
+        self._states, self._graphs, self._seen = {}, {}, set()
+        self._host_pos = 0
+        self.read_back = True           # probes: False leaves the record on the device (no copy, the caller must not read it)
+        self.steps = 0
+
+    def _state(self, ns: int, sampled: bool) -> _SpecState:
+        st = self._states.get((ns, sampled))
+        if st is None:
+            i, base = self._ints, self._ints.data_ptr()
+            st = self._states[(ns, sampled)] = _SpecState(
+                ctypes.sizeof(_SpecState), self.k, self.n_slots, self.attn_chunk, ns, self.ngram_max, self.ngram_min,
+                base, base + 4 * 16, base + 4 * 32, base + 4 * 48, base + 4 * 64, base + 4 * 80, base + 4 * 81, self.history.data_ptr(),
+                base + 4 * 84, self.logits.data_ptr() if (sampled or self.keep_logits) else None,
+                self._part_val.data_ptr(), self._part_idx.data_ptr(), self._ws.data_ptr() + self._ws_off, self._ws.numel() - self._ws_off)
+        return st
+
+    def splits(self, ctx: int) -> int:
+        """Power-of-two split count whose splits * attn_chunk positions cover ``ctx`` keys (at most 64)."""
+        ns = 1
+        while ns * self.attn_chunk < ctx and ns < 64:
+            ns *= 2
+        return ns
+
+    def arm(self, sampling) -> None:
+        """Greedy (None) or the given ``SamplingParams`` for the following steps (every row draws with the request's row)."""
+        self._sampled = sampling is not None
+        if self._sampled:
+            from .sampling import pack
+            self._params.copy_(pack([sampling] * (self.k + 1), self.dev))
+
+    def seed(self, history, remaining: int, drafts=None) -> None:
+        """The sequence so far (its KV cache holds all but the last token; the last token is the next step's first row) and the
+        number of tokens still to emit.  The first step's drafts: ``speculative.propose`` on the host, or ``drafts``."""
+        from .speculative import propose
+        n = len(history)
+        if not 1 <= n <= self.max_len:
+            raise ValueError("SpecStep.seed: history empty or longer than max_len")
+        if min(history) < 0 or max(history) >= self.cfg.vocab_size:
+            raise ValueError("SpecStep.seed: token outside the vocabulary")
+        k, P = self.k, n - 1
+        d = list(drafts) if drafts is not None else propose(history, k, self.ngram_max, self.ngram_min)[0]
+        if len(d) != k:
+            raise ValueError(f"SpecStep.seed: {len(d)} drafts for k = {k}")
+        torch.cuda.current_stream(self.dev).synchronize()          # (the pinned staging block may still be in flight)
+        h = self._h_ints.numpy()
+        h[:] = 0
+        h[0], h[1:k + 1] = history[-1], d
+        h[16:32] = self.slot
+        h[32:33 + k] = range(P, P + k + 1)
+        h[48:48 + k] = d
+        h[80], h[81] = P, int(remaining)
+        self._ints.copy_(self._h_ints, non_blocking=True)
+        self.history[:n].copy_(torch.tensor(list(history), dtype=torch.int32), non_blocking=False)
+        self._host_pos = P
+
+    def set_drafts(self, drafts) -> None:
+        """Replace the next step's drafts (teacher forcing, oracle / adversarial drafts)."""
+        d = [int(t) for t in drafts]
+        if len(d) != self.k or min(d) < 0 or max(d) >= self.cfg.vocab_size:
+            raise ValueError(f"SpecStep: need {self.k} draft tokens inside the vocabulary")
+        torch.cuda.current_stream(self.dev).synchronize()          # (the pinned staging row may still be in flight)
+        self._h_drafts.numpy()[:self.k] = d
+        self._ints[1:self.k + 1].copy_(self._h_drafts[:self.k], non_blocking=True)
+        self._ints[48:48 + self.k].copy_(self._h_drafts[:self.k], non_blocking=True)
+
+    def _launch(self, st, sampled: bool):
+        with torch.cuda.device(self.dev):
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            if sampled:
+                rc = self.lib.onebit_spec_step_sampled(ctypes.addressof(self._model), ctypes.addressof(st), self._params.data_ptr(), stream)
+            else:
+                rc = self.lib.onebit_spec_step(ctypes.addressof(self._model), ctypes.addressof(st), stream)
+        _lib.check(rc, "onebit_spec_step_sampled" if sampled else "onebit_spec_step")
+        if self.read_back:
+            self._rec_host.copy_(self._rec_dev, non_blocking=True)
+
+    def step(self, drafts=None, ns: Optional[int] = None) -> None:
+        """Enqueue one speculative step (asynchronous).  ``ns``: attention splits (default: what covers the host-known position
+        + k + 1 keys).  ``drafts``: override the device-side drafts of this step."""
+        if drafts is not None:
+            self.set_drafts(drafts)
+        if ns is None:
+            ns = self.splits(self._host_pos + self.k + 1)
+        key = (ns, self._sampled, self.read_back)
+        g = self._graphs.get(key)
+        if g is not None:
+            g.replay()
+        else:
+            st = self._state(ns, self._sampled)
+            self._launch(st, self._sampled)                        # this step; its graph is captured for the next ones
+            if self._use_graph and key in self._seen:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._launch(st, self._sampled)
+                self._graphs[key] = g
+            self._seen.add(key)
+        self.steps += 1
+
+    def read_record(self):
+        """Wait for the enqueued steps and return the last one's commit record ``(n_acc, pos, n_drafted)``: the step emitted
+        ``n_acc + 1`` tokens (-1: nothing -- no budget or the cache is full), ``pos`` is the position of the sequence's last token."""
+        torch.cuda.current_stream(self.dev).synchronize()
+        r = self._rec_host.numpy()
+        self._host_pos = int(r[1])
+        return int(r[0]), int(r[1]), int(r[2])

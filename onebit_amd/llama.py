@@ -481,7 +481,7 @@ class OneBitLlamaForCausalLM(nn.Module):
 
 
 def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None, pad_token_id=None, do_sample: bool = False,
-                     temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed=None) -> torch.Tensor:
+                     temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed=None, speculative=None) -> torch.Tensor:
     """``generate`` on the native engines, same return contract: B = 1 -> ``DecodeEngine`` (the prompt through ``onebit_mixed_step``,
     every further token one HIP-graph replay of ``onebit_decode_step``); B > 1 -> ``ContinuousBatcher`` with one slot per row (the
     prompts enter in ONE mixed step, decode-only steps replay the batched step's graph).  The steps are enqueued without looking at
@@ -489,12 +489,17 @@ def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_tok
     output ends where every row is finished: generation/utils.py:2543-2570).  Engines are kept per (batch, max_len) on the model.
     Greedy tokens equal ``generate``'s up to fp16 near-ties of the logits (the engines' kernels sum in another order).
     ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: as ``generate`` -- row b draws with the seed and stream b, token
-    n of the sequence at n -- so the sampled tokens equal ``generate``'s up to near-ties of the perturbed scores."""
+    n of the sequence at n -- so the sampled tokens equal ``generate``'s up to near-ties of the perturbed scores.
+    ``speculative`` (``onebit_amd.speculative.SpecConfig``): B = 1 only -- several tokens per pass over the weights where the
+    sequence's own history predicts them (``DecodeEngine.generate(..., speculative=)``); the tokens are those of the verify pass."""
     from .engine import DecodeEngine
     from .serving import ContinuousBatcher
     if input_ids.dim() != 2:
         raise ValueError("input_ids must be [B, S]")
     B, S = input_ids.shape
+    if speculative is not None and B > 1:
+        raise NotImplementedError("generate_native: speculative decoding is single-stream (B = 1); the batched step "
+                                  "(ContinuousBatcher) does not speculate")
     if max_new_tokens < 1:
         return input_ids
     eos = None
@@ -522,7 +527,10 @@ def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_tok
             if len(engines) >= 4:
                 engines.clear()
             eng = engines[key] = DecodeEngine(self, max_len=key[1])
-        rows = [eng.generate(input_ids, max_new_tokens, sampling=sp)[0, S:].tolist()]
+        if speculative is None:
+            rows = [eng.generate(input_ids, max_new_tokens, sampling=sp)[0, S:].tolist()]
+        else:
+            rows = [eng.generate(input_ids, max_new_tokens, sampling=sp, speculative=speculative)[0, S:].tolist()]
     else:
         cb = engines.get(key)
         if cb is None:
