@@ -89,6 +89,13 @@ int onebit_unpack_signs(const void *packed, void *out, int dtype, int64_t N, int
  *   the register-staged GEMM runs instead, same results.
  */
 size_t onebit_linear_workspace_bytes(int64_t T, int64_t K, int64_t N, int dtype);
+/* Which kernels an fp32 (ONEBIT_F32) call of onebit_linear_forward / onebit_matmul_partial(_ws) with this shape and
+ * packed row pitch takes: 0 = the generic kernel (any K % 8 == 0, any pitch), 1 = the fp32 GEMV (T == 1, K % 128 == 0,
+ * K <= 16384, 16-byte aligned pitch), 2 = the tiled fp32-MFMA GEMM (K % 32 == 0, 4-byte aligned pitch).  A pure function
+ * of its arguments: no device is queried.  The call itself also needs a 4-byte (GEMV: 16-byte, else it takes the GEMM)
+ * aligned packed pointer and 16-byte aligned activation rows; without them it runs the generic kernel.  The fp32 route
+ * needs no workspace. */
+int onebit_linear_f32_route(int64_t T, int64_t K, int64_t N, int64_t ldw_bytes);
 int onebit_linear_forward(const void *packed, int64_t ldw_bytes, const void *x, const void *h,
                           const void *g, const void *bias_or_null, void *y, void *u_or_null,
                           void *workspace, size_t workspace_bytes, int64_t T, int64_t K,

@@ -30,6 +30,7 @@ SYMBOLS = {
     "onebit_fp16_to_int8": (_int, [_vp, _int, _vp, _i64, _i64, _vp]),
     "onebit_unpack_signs": (_int, [_vp, _vp, _int, _i64, _i64, _vp]),
     "onebit_linear_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64, _int]),
+    "onebit_linear_f32_route": (_int, [_i64, _i64, _i64, _i64]),
     "onebit_linear_forward": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
                                      _i64, _i64, _i64, _int, _f, _u, _vp]),
     "onebit_matmul_partial": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _int, _vp]),

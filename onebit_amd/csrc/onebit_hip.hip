@@ -21,6 +21,7 @@
 #include "ob_batch.h"
 #include "ob_train.h"
 #include "ob_flash.h"
+#include "ob_f32.h"
 
 // row kernels are instantiated per number of populated 8-half vectors per thread (ceil(width / 4096), 1..4)
 #define OB_NV_DISPATCH(WIDTH, CALL1, CALL2, CALL3, CALL4) \
@@ -392,6 +393,80 @@ extern "C" size_t onebit_linear_workspace_bytes(int64_t T, int64_t K, int64_t N,
     return ob_required_workspace(T, K, N, dtype);
 }
 
+// ------------------------------------------------------------------ fp32 route (ob_f32.h) --
+// 0 = generic kernels, 1 = GEMV, 2 = tiled MFMA GEMM: a pure function of the shape (no device query)
+extern "C" int onebit_linear_f32_route(int64_t T, int64_t K, int64_t N, int64_t ldw_bytes)
+{
+    if (T <= 0 || K <= 0 || N <= 0) return 0;
+    if (K % 32 != 0 || ldw_bytes % 4 != 0 || ldw_bytes < K / 8) return 0;
+    if (T > 0x7fffffffLL / 16 || N > 0x7fffffffLL / 16 || K > 0x7fffffffLL) return 0;
+    if (T == 1 && K % 128 == 0 && K <= OB_F32_GEMV_MAXK && ldw_bytes % 16 == 0) return 1;
+    return 2;
+}
+
+// tile of the GEMM for a shape: RT token tiles per wave; `big` = the 128 x 64 tile (from one round of them over the chip)
+static inline void ob_f32_gemm_tile(int64_t T, int64_t N, int &rt, bool &big)
+{
+    rt = T <= 16 ? 1 : T <= 32 ? 2 : 4;
+    big = rt == 4 && ((N + 127) / 128) * ((T + 63) / 64) >= OB_F32_CUS;
+}
+
+// the route this CALL takes: the shape's, unless the pointers rule it out
+static int ob_f32_route(const void *packed, int64_t ldw_bytes, const void *x, int64_t ldx, int64_t T, int64_t K, int64_t N)
+{
+    int route = onebit_linear_f32_route(T, K, N, ldw_bytes);
+    if (!route || !ob_aligned(packed, 4) || !ob_aligned(x, 16) || ldx % 4 != 0) return 0;
+    if (route == 1 && !ob_aligned(packed, 16)) route = 2;
+    if (route == 2) {
+        int rt; bool big;
+        ob_f32_gemm_tile(T, N, rt, big);
+        if (((N + 31) / 32) * ((T + 16 * rt - 1) / (16 * rt)) > 0x7fffffffLL) return 0;
+    }
+    return route;
+}
+
+// z (PARTIAL) or u = z * g, fp32, on the route ob_f32_route chose
+template <bool PARTIAL>
+static void ob_launch_f32(int route, const void *packed, int64_t ldw_bytes, const void *x, int64_t ldx, const void *h,
+                          const void *g, float *out, int64_t T, int64_t K, int64_t N, hipStream_t s)
+{
+    if (route == 1) {
+        static bool attr_set[OB_MAX_DEVICES] = {};
+        ob_set_max_lds_once(ob_f32_gemv_kernel<PARTIAL>, attr_set, (int)OB_F32_GEMV_LDS(OB_F32_GEMV_MAXK));
+        const int64_t rows_wg = (K >> 7) <= 32 ? 32 : 16;
+        const int64_t grid = std::min<int64_t>((N + rows_wg - 1) / rows_wg, 2 * (int64_t)ob_cu_count());
+        hipLaunchKernelGGL((ob_f32_gemv_kernel<PARTIAL>), dim3((unsigned)grid), dim3(256), OB_F32_GEMV_LDS(K), s,
+                           (const uint8_t *)packed, ldw_bytes, (const float *)x, (const float *)h, (const float *)g, out, (int)K, (int)N);
+        return;
+    }
+    int rt; bool big;
+    ob_f32_gemm_tile(T, N, rt, big);
+    const int vec_out = (N % 4 == 0 && ob_aligned(out, 16)) ? 1 : 0;
+#define OB_F32_GO(WN_, WK_, RN_, RT_)                                                                              \
+    do {                                                                                                           \
+        const int nbn = (int)((N + WN_ * RN_ * 16 - 1) / (WN_ * RN_ * 16));                                        \
+        const int nbt = (int)((T + RT_ * 16 - 1) / (RT_ * 16));                                                    \
+        hipLaunchKernelGGL((ob_f32_gemm_kernel<PARTIAL, WN_, WK_, RN_, RT_>), dim3((unsigned)(nbn * nbt)), dim3(256), 0, s, \
+                           (const uint32_t *)packed, ldw_bytes / 4, (const float *)x, ldx, (const float *)h,       \
+                           (const float *)g, out, (int)T, (int)K, (int)N, nbn, vec_out);                           \
+    } while (0)
+    if (big) OB_F32_GO(4, 1, 2, 4);
+    else if (rt == 4) OB_F32_GO(1, 4, 2, 4);
+    else if (rt == 2) OB_F32_GO(1, 4, 2, 2);
+    else OB_F32_GO(1, 4, 2, 1);
+#undef OB_F32_GO
+}
+
+// fp32 LayerNorm of u rows (in place when y == uin): rows-in-registers kernel when the shape allows, else the generic one
+static void ob_launch_ln_f32(const float *uin, const float *bias, float *y, int64_t T, int64_t N, float eps, hipStream_t s)
+{
+    if (N % 4 == 0 && N <= OB_F32_LN_MAXN && ob_aligned(uin, 16) && ob_aligned(y, 16) && (!bias || ob_aligned(bias, 16)))
+        hipLaunchKernelGGL(ob_f32_ln_rows_kernel, dim3((unsigned)T), dim3(256), 0, s, uin, bias, y, (float *)nullptr, (int)N, eps, 0);
+    else
+        hipLaunchKernelGGL((ob_layernorm_kernel<float, false>), dim3((unsigned)T), dim3(256), 0, s, (const float *)nullptr, uin,
+                           (const float *)nullptr, bias, y, (float *)nullptr, (int)N, eps, 0);
+}
+
 extern "C" int onebit_linear_forward(const void *packed, int64_t ldw_bytes, const void *x,
                                      const void *h, const void *g, const void *bias, void *y,
                                      void *u_or_null, void *workspace, size_t workspace_bytes,
@@ -523,7 +598,21 @@ extern "C" int onebit_linear_forward(const void *packed, int64_t ldw_bytes, cons
                                (_Float16 *)y, (_Float16 *)u_or_null, T, N, ln_eps, skip, s);
         return ob_launch_status("linear_forward(layernorm)");
     }
-    // F32: z (fp32) staged in y, then g / LayerNorm in place.
+    // F32, eligible shape: GEMV / MFMA GEMM write u = z * g into u_or_null (or y), the row LayerNorm reads it once
+    const int f32_route = K > 0 ? ob_f32_route(packed, ldw_bytes, x, K, T, K, N) : 0;
+    if (f32_route) {
+        float *ubuf = (float *)(u_or_null ? u_or_null : y);
+        ob_launch_f32<false>(f32_route, packed, ldw_bytes, x, K, h, g, ubuf, T, K, N, s);
+        rc = ob_launch_status(f32_route == 1 ? "linear_forward(f32 gemv)" : "linear_forward(f32 gemm)");
+        if (rc) return rc;
+        if (skip) {
+            if (ubuf != y) (void)hipMemcpyAsync(y, ubuf, (size_t)T * N * 4, hipMemcpyDeviceToDevice, s);
+            return 0;
+        }
+        ob_launch_ln_f32(ubuf, (const float *)bias, (float *)y, T, N, ln_eps, s);
+        return ob_launch_status("linear_forward(f32 layernorm)");
+    }
+    // F32, any other shape: z (fp32) staged in y, then g / LayerNorm in place.
     float *zbuf = (float *)y;
     if (K == 0) {
         (void)hipMemsetAsync(zbuf, 0, (size_t)T * N * 4, s);
@@ -564,6 +653,8 @@ extern "C" int onebit_matmul_partial_ws(const void *packed, int64_t ldw_bytes, c
         ob_launch_mm16<true>(packed, ldw_bytes, x, ldx, h, nullptr, nullptr, zp, T, K, N, s);
     else if (dtype == ONEBIT_F16)
         ob_launch_simple<_Float16>(packed, ldw_bytes, x, ldx, h, zp, T, K, N, s);
+    else if (const int f32_route = ob_f32_route(packed, ldw_bytes, x, ldx, T, K, N))
+        ob_launch_f32<true>(f32_route, packed, ldw_bytes, x, ldx, h, nullptr, zp, T, K, N, s);
     else
         ob_launch_simple<float>(packed, ldw_bytes, x, ldx, h, zp, T, K, N, s);
     return ob_launch_status("matmul_partial");
