@@ -655,6 +655,43 @@ int onebit_train_backward(const void *gy, const void *x, const void *w_latent, c
                           void *gbias_or_null, void *workspace, size_t workspace_bytes, int64_t T, int64_t K,
                           int64_t N, int dtype, void *stream);
 
+/* ---- knowledge-distillation loss: the objective the train-mode layer is trained against (KDTrainer.compute_loss,
+ * llamafactory/kd.py:34-113).  Additive to ABI 10.  Rows are contiguous ([T, V] / [T, H], `dtype` ONEBIT_F16 / ONEBIT_F32),
+ * the arithmetic is fp32, all memory is the caller's, nothing is allocated and nothing synchronises (graph-capture safe).
+ * No atomics: rows are summed in a fixed order, so results are bit-reproducible.  Rows whose base and pitch keep groups
+ * of four elements aligned take vector loads, any other pitch (V = 32001, 32003) an element-wise path.
+ * Errors before any launch: unknown dtype ONEBIT_E_DTYPE, V / H <= 0 ONEBIT_E_SHAPE, a null required pointer or T < 0
+ * ONEBIT_E_ARG, the hidden loss's stats not 16-byte aligned ONEBIT_E_ALIGN; T == 0 returns 0 and writes nothing.
+ *
+ * token loss   row r holds V student and V teacher logits and, with `labels` [T] (int64, nullable), the label it is scored
+ *              against (the caller has applied the causal shift); a label equal to `ignore_index` leaves the row unlabelled.
+ *   forward    stats [T, ONEBIT_KD_TOKEN_STATS] fp32 = {max_s, log z_s, max_t, log z_t, kl_row, ce_row}, lse = max + log z kept
+ *              as its two parts: x - lse is formed as (x - max) - log z, which keeps the bits of log z that the sum would
+ *              round away at large logits (ulp(6e4) = 0.004, a relative error of every probability of the row):
+ *                kl_row = sum_v p_t[v] * ((t[v] - lse_t) - (s[v] - lse_s)), an entry with p_t[v] == 0 (teacher logit -inf)
+ *                adds exactly 0 as F.kl_div's xlogy does;  ce_row = lse_s - s[label] on labelled rows, else 0.
+ *              sums [3] fp32 = {sum kl_row, sum of ce_row over labelled rows, number of labelled rows}.
+ *              Each logits tensor is read from HBM once for V <= 32768 (both rows stay in registers between the passes).
+ *              `teacher` may be NULL (the KL term switched off): the teacher is not read, kl_row = 0, and backward
+ *              (NULL there too, or coef[0] == 0) forms the cross-entropy part alone.
+ *   backward   grad[r, v] = coef[0] * (p_s - p_t) + coef[1] * (p_s - [v == label]) (second term on labelled rows only), p_s and
+ *              p_t rebuilt from the saved (max, log z).  coef [2] fp32 lives in DEVICE memory (upstream gradient folded in without a
+ *              host sync) and is applied in fp32 before the one rounding to `dtype`.  coef[0] == 0 skips the teacher.
+ * hidden loss  d_r = | t / max(|t|, 1e-12) - s / max(|s|, 1e-12) |^2 per row, as a sum of squared differences.
+ *   forward    stats [T, ONEBIT_KD_HIDDEN_STATS] fp32 = {|s|, |t|, d_r, s^ . (t^ - s^)};  sums [3] = {sum d_r, 0, 0}.
+ *   backward   grad[r] = coef[0] * -(2 / |s|) * (delta - s^ (s^ . delta)), delta = t^ - s^;  coef [1] fp32 in device memory. */
+#define ONEBIT_KD_TOKEN_STATS 6
+#define ONEBIT_KD_HIDDEN_STATS 4
+int onebit_kd_token_forward(const void *student, const void *teacher_or_null, const int64_t *labels_or_null, float *stats,
+                            float *sums, int64_t T, int64_t V, int dtype, int64_t ignore_index, void *stream);
+int onebit_kd_token_backward(const void *student, const void *teacher_or_null, const int64_t *labels_or_null, const float *stats,
+                             const float *coef, void *grad, int64_t T, int64_t V, int dtype, int64_t ignore_index,
+                             void *stream);
+int onebit_kd_hidden_forward(const void *student, const void *teacher, float *stats, float *sums, int64_t T, int64_t H,
+                             int dtype, void *stream);
+int onebit_kd_hidden_backward(const void *student, const void *teacher, const float *stats, const float *coef, void *grad,
+                              int64_t T, int64_t H, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ FLAG_Q_TOKEN_MAJOR = 2      # onebit_rows_qkv_rope
 FLAG_PRESCALED = 4
 FLAG_TILE_STATS = 8
 ABI_VERSION = 10
+KD_TOKEN_STATS, KD_HIDDEN_STATS = 6, 4      # floats per row of the KD losses' stats tensors (ONEBIT_KD_*_STATS)
 
 # name -> (restype, argtypes); must list every symbol include/onebit.h declares
 _i64, _vp, _int, _f, _u = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_uint
@@ -81,6 +82,11 @@ SYMBOLS = {
     "onebit_train_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64, _int]),
     "onebit_train_forward": (_int, [_vp] * 8 + [_i64, _i64, _i64, _int, _f, _vp]),
     "onebit_train_backward": (_int, [_vp] * 13 + [ctypes.c_size_t, _i64, _i64, _i64, _int, _vp]),
+    # knowledge-distillation loss (additive to ABI 10)
+    "onebit_kd_token_forward": (_int, [_vp] * 5 + [_i64, _i64, _int, _i64, _vp]),      # (s, t, labels, stats, sums, T, V, dtype, ignore, stream)
+    "onebit_kd_token_backward": (_int, [_vp] * 6 + [_i64, _i64, _int, _i64, _vp]),     # (s, t, labels, stats, coef, grad, T, V, dtype, ignore, stream)
+    "onebit_kd_hidden_forward": (_int, [_vp] * 4 + [_i64, _i64, _int, _vp]),           # (s, t, stats, sums, T, H, dtype, stream)
+    "onebit_kd_hidden_backward": (_int, [_vp] * 5 + [_i64, _i64, _int, _vp]),          # (s, t, stats, coef, grad, T, H, dtype, stream)
 }
 
 _lock = threading.Lock()
