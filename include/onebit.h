@@ -692,6 +692,40 @@ int onebit_kd_hidden_forward(const void *student, const void *teacher, float *st
 int onebit_kd_hidden_backward(const void *student, const void *teacher, const float *stats, const float *coef, void *grad,
                               int64_t T, int64_t H, int dtype, void *stream);
 
+/* ---- SVID start checkpoints: a teacher projection A [N, K] (fp16 / fp32, row pitch `lda` elements, K % 8 == 0, base 16-byte
+ * aligned, lda % 8 == 0) -> weight_scale w [N], input_factor h [K] by the rank-1 NMF of |A| that the reference fits with
+ * sklearn (scripts/build_start_ckpt.py:21-34; for one component its coordinate descent is alternating least squares), and
+ * sign(A) as latent weights and / or packed bits.  Additive to ABI 10.  fp32 arithmetic, |A| is never materialised, no atomics
+ * (every sum has a fixed order: bit-reproducible), caller-owned memory, stream-ordered, nothing allocated.
+ *
+ * onebit_svid_iterate  ONE alternating iteration, w and h (fp32, h 16-byte aligned) updated in place:
+ *     hh = h.h ; xh = |A| h ; viol  = sum_i |pg(w_i, w_i hh - xh_i)| ; w = max(xh / hh, 0)   (w kept when hh == 0)
+ *     ww = w.w ; xw = |A|^T w ; viol += sum_j |pg(h_j, h_j ww - xw_j)| ; h = max(xw / ww, 0) (h kept when ww == 0)
+ *     pg(v, g) = v == 0 ? min(0, g) : g
+ *   stats (device, fp32 [ONEBIT_SVID_STATS]) = {viol, hh, ww, h.h of the updated h}.  The caller reads viol back once per
+ *   iteration to apply sklearn's stopping rule (viol / viol of iteration 1 <= tol): a host synchronisation per iteration, so
+ *   this path is for offline tools and is not meant for graph capture.  Non-finite input shows as a non-finite viol.
+ *   route 1 (one pass): one kernel reads A once, a workgroup per band of rows with h and its column sums in registers; covers
+ *   K <= ONEBIT_SVID_ONEPASS_MAX_K.  route 2 (two passes): a row kernel and a column kernel, any K.  Both are followed by
+ *   two small launches over the partials (column finalize, statistics): 3 / 4 launches per call.  route 0 picks
+ *   onebit_svid_route(N, K, dtype) (needs no device).  Forcing route 1 beyond its bound is ONEBIT_E_ARG.
+ * onebit_svid_emit     one read of A; each output is skipped when its pointer is NULL:
+ *     latent  [N, K] contiguous, `latent_dtype`: sign(a) * scale, a zero of either sign (and NaN) gives 0 as torch.sign does
+ *     packed  int8 [N, K / 8], what onebit_pack_signs gives: LSB first, bit = 1 for a < 0, zero and NaN pack as +1
+ *     sums    device fp32 [2] = {sum (|a_ij| - w_i h_j)^2, sum a_ij^2} (needs w, h and the workspace)
+ * workspace: onebit_svid_workspace_bytes(N, K, dtype) covers both calls and both routes; 16-byte aligned.
+ * Errors before any launch: K % 8 != 0 ONEBIT_E_SHAPE, a null required pointer, N < 1 or lda < K ONEBIT_E_ARG, alignment
+ * ONEBIT_E_ALIGN, unknown dtype ONEBIT_E_DTYPE, a short workspace ONEBIT_E_WSPACE.                                          */
+#define ONEBIT_SVID_STATS 4
+#define ONEBIT_SVID_ONEPASS_MAX_K 16384
+size_t onebit_svid_workspace_bytes(int64_t N, int64_t K, int dtype);
+int onebit_svid_route(int64_t N, int64_t K, int dtype);
+int onebit_svid_iterate(const void *A, int dtype, int64_t lda, float *w, float *h, float *stats, void *workspace,
+                        size_t workspace_bytes, int64_t N, int64_t K, int route, void *stream);
+int onebit_svid_emit(const void *A, int dtype, int64_t lda, const float *w, const float *h, void *latent_or_null,
+                     int latent_dtype, float scale, void *packed_or_null, float *sums_or_null, void *workspace,
+                     size_t workspace_bytes, int64_t N, int64_t K, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ FLAG_PRESCALED = 4
 FLAG_TILE_STATS = 8
 ABI_VERSION = 10
 KD_TOKEN_STATS, KD_HIDDEN_STATS = 6, 4      # floats per row of the KD losses' stats tensors (ONEBIT_KD_*_STATS)
+SVID_STATS, SVID_ONEPASS_MAX_K = 4, 16384   # ONEBIT_SVID_STATS, ONEBIT_SVID_ONEPASS_MAX_K
 
 # name -> (restype, argtypes); must list every symbol include/onebit.h declares
 _i64, _vp, _int, _f, _u = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_uint
@@ -87,6 +88,11 @@ SYMBOLS = {
     "onebit_kd_token_backward": (_int, [_vp] * 6 + [_i64, _i64, _int, _i64, _vp]),     # (s, t, labels, stats, coef, grad, T, V, dtype, ignore, stream)
     "onebit_kd_hidden_forward": (_int, [_vp] * 4 + [_i64, _i64, _int, _vp]),           # (s, t, stats, sums, T, H, dtype, stream)
     "onebit_kd_hidden_backward": (_int, [_vp] * 5 + [_i64, _i64, _int, _vp]),          # (s, t, stats, coef, grad, T, H, dtype, stream)
+    # SVID start checkpoints (additive to ABI 10)
+    "onebit_svid_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _int]),
+    "onebit_svid_route": (_int, [_i64, _i64, _int]),
+    "onebit_svid_iterate": (_int, [_vp, _int, _i64, _vp, _vp, _vp, _vp, ctypes.c_size_t, _i64, _i64, _int, _vp]),   # (A, dtype, lda, w, h, stats, ws, ws_bytes, N, K, route, stream)
+    "onebit_svid_emit": (_int, [_vp, _int, _i64, _vp, _vp, _vp, _int, _f, _vp, _vp, _vp, ctypes.c_size_t, _i64, _i64, _vp]),   # (A, dtype, lda, w, h, latent, latent_dtype, scale, packed, sums, ws, ws_bytes, N, K, stream)
 }
 
 _lock = threading.Lock()

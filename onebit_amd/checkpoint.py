@@ -74,10 +74,15 @@ def load_inference_checkpoint(path: str, device="cuda", dtype=torch.float16) -> 
     return model.to(device).eval()
 
 
-def save_inference_checkpoint(model: OneBitLlamaForCausalLM, path: str) -> Tuple[str, str]:
+def write_checkpoint(path: str, config: dict, sd: Dict[str, torch.Tensor]) -> Tuple[str, str]:
+    """the on-disk layout: ``config.json`` (indent 2) and ``pytorch_model.bin`` (torch pickle of CPU tensors)"""
     os.makedirs(path, exist_ok=True)
     cfg_path, w_path = os.path.join(path, "config.json"), os.path.join(path, WEIGHTS_NAME)
     with open(cfg_path, "w") as f:
-        json.dump(config_to_json(model.config), f, indent=2)
-    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, w_path)
+        json.dump(config, f, indent=2)
+    torch.save({k: v.detach().cpu() for k, v in sd.items()}, w_path)
     return cfg_path, w_path
+
+
+def save_inference_checkpoint(model: OneBitLlamaForCausalLM, path: str) -> Tuple[str, str]:
+    return write_checkpoint(path, config_to_json(model.config), model.state_dict())
