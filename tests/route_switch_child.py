@@ -211,10 +211,15 @@ def wl_mixed():
 
 
 def wl_train():
-    """the fp16 train-mode layer (forward and backward) against its fp64 restatement, at the shapes of test_gpu_train.py"""
+    """the fp16 train-mode layer (forward and backward) against its fp64 restatement, at the shapes of test_gpu_train.py, and
+    element by element over the case table of test_gpu_train_elementwise.py"""
     import test_gpu_train
+    import test_gpu_train_elementwise
+    from _train_ref import CASE_IDS
     for (T, K, N) in ((256, 1024, 768), (77, 200, 136), (5, 24, 8), (300, 1000, 520), (129, 130, 131)):
         test_gpu_train.test_fp16_against_restatement_in_fp64(T, K, N)
+    for case_id in CASE_IDS:
+        test_gpu_train_elementwise.test_elementwise_parity(case_id, "float16")
     return {}
 
 
