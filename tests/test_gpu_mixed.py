@@ -218,7 +218,8 @@ def test_mixed_step_tokens_equal_single_sequence_generate(golden_dir, chunk):
 
 def test_mixed_step_logits_against_the_module_path(golden_dir):
     """One mixed step (2 decode rows with history + 3 prompt chunks, one of them continuing a half-entered prompt) on the tiny golden
-    model: fp16 logits of every item's last row against the module path run per sequence (eager attention, reference op order)."""
+    model: fp16 logits of every item's last row against the module path run per sequence (eager attention, reference op order).
+    (The comparison with the REFERENCE's recorded logits, under the bar derived from its own goldens: tests/test_gpu_mixed_reference.py.)"""
     from onebit_amd.engine import MixedStep
     dev = torch.device(DEV)
     model = _tiny(golden_dir, "b", dev)
@@ -271,7 +272,8 @@ def test_mixed_step_mid_size_routes(hidden, inter, heads, rows):
     """A few hundred rows at 13B / 7B widths (7B down_proj: K = 11008 splits into 5632 + 5376): q|k|v and gate|up take pre-scaled rows because the GROUP fills the chip (ob_gemm3_group_ok),
     o_proj / down_proj run as two K-slices whose fp32 sums the next row kernel adds (ob_gemm3_ksplit2); 65 .. 320 rows: every projection
     as balanced passes of <= 64 rows through the LDS-DMA skinny GEMM.  Logits of the prompt's last row and of the decode rows against
-    the module path."""
+    the module path.  (The same routes at 7B widths against the REFERENCE's recorded logits -- a 4096-token prompt cut into chunks of
+    93 .. 1076 rows next to decoding slots: tests/test_gpu_mixed_reference.py.)"""
     from onebit_amd.llama import OneBitLlamaConfig, build_synthetic_model
     from onebit_amd.engine import MixedStep
     dev = torch.device(DEV)
@@ -440,7 +442,8 @@ def test_mixed_step_full_size_properties():
     fixed-order combines, tickets back at zero, the same cache rows rewritten); (2) the ORDER of the items does not matter: every item's
     logits are bit-identical under a permutation (a row's sums never mix with other rows': the GEMM's token columns, the row kernels, the
     ragged attention's segments are independent); (3) a prompt entering as one 512-token chunk or as 256 + 256 gives the same greedy token
-    and logits within fp16 tolerance (the attention's key blocks split differently)."""
+    and logits within fp16 tolerance (the attention's key blocks split differently).  (Properties of the step itself; its logits against
+    the REFERENCE's recorded ones, chunked prompts included: tests/test_gpu_mixed_reference.py.)"""
     from onebit_amd.engine import MixedStep
     from onebit_amd.llama import OneBitLlamaConfig, build_synthetic_model
     dev = torch.device(DEV)
