@@ -726,6 +726,29 @@ int onebit_svid_emit(const void *A, int dtype, int64_t lda, const float *w, cons
                      int latent_dtype, float scale, void *packed_or_null, float *sums_or_null, void *workspace,
                      size_t workspace_bytes, int64_t N, int64_t K, void *stream);
 
+/* ---- Train-mode causal self-attention (additive to ABI 10; csrc/ob_flash_train.h) ------------------------------------------
+ * Causal self-attention of S tokens per sequence with no KV cache, forward and backward, fp16, head_dim 64 or 128, GQA
+ * (n_kv_heads divides n_heads): scores = q k^T / sqrt(head_dim) + causal mask, softmax in fp32, probabilities . v
+ * (modeling_bitllama.py:389-406).  Flash style in both directions: no [S, S] tensor in memory.  No atomics: results are
+ * bit-reproducible from call to call.
+ *   q, o, d_o, dq  [B, S, n_heads, head_dim]     contiguous, token-major, 16-byte aligned
+ *   k, v, dk, dv   [B, S, n_kv_heads, head_dim]  contiguous, token-major, 16-byte aligned
+ *   lse            fp32 [B, n_heads, S]: natural log of sum_j exp(score_ij) over the keys j <= i
+ * onebit_attention_train_forward   writes o and lse.
+ * onebit_attention_train_backward  reads what the forward read and wrote plus d_o, writes dq, dk, dv in three launches
+ *   (delta = sum_j P_ij dP_ij into the workspace -- rowsum(d_o . o) in exact arithmetic, formed from the recomputed P so that it
+ *   cancels against dP; o is checked but not read --, dK / dV, dQ).  workspace: onebit_attention_train_workspace_bytes (needs no
+ *   device; >= 256, non-decreasing in every size), 16-byte aligned.
+ * Errors before any launch: negative sizes or heads < 1 or a null pointer ONEBIT_E_ARG, head_dim not in {64, 128} or
+ * n_heads % n_kv_heads != 0 ONEBIT_E_SHAPE, alignment ONEBIT_E_ALIGN, a short workspace ONEBIT_E_WSPACE.  B == 0 or S == 0
+ * returns 0 and touches nothing.                                                                                             */
+int onebit_attention_train_forward(const void *q, const void *k, const void *v, void *o, float *lse, int64_t B, int64_t S,
+                                   int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, void *stream);
+size_t onebit_attention_train_workspace_bytes(int64_t B, int64_t S, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim);
+int onebit_attention_train_backward(const void *q, const void *k, const void *v, const void *o, const float *lse, const void *d_o,
+                                    void *dq, void *dk, void *dv, void *workspace, size_t workspace_bytes, int64_t B, int64_t S,
+                                    int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

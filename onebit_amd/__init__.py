@@ -7,10 +7,13 @@ Public surface mirrors the reference's for this path:
   KDLoss / kd_token_loss / kd_hidden_loss   knowledge-distillation objective (reference: llamafactory/kd.py:34-113)
   svid_decompose / build_start_state_dict / build_inference_state_dict   SVID start checkpoints from a teacher
                                 (reference: scripts/build_start_ckpt.py)
+  OneBitLlamaForCausalLMTrain / flash_attention_train   the train-mode model on train.BitLinear and its causal attention with
+                                a flash-style HIP forward and backward (reference: modeling_bitllama.py BitLlamaForCausalLM)
 """
 from .bitnet import BitLinearInf, OneBitLinear, fp16_to_int8, int8_to_fp16, pack_signs  # noqa: F401
 from .kd import KDLoss, kd_hidden_loss, kd_token_loss  # noqa: F401
 from .svid import (SvidResult, build_inference_state_dict, build_start_state_dict, svid_decompose, svid_init,  # noqa: F401
                    svid_start_layer)
+from .train_model import OneBitLlamaForCausalLMTrain, eager_attention_train, flash_attention_train  # noqa: F401
 
 __version__ = "0.1.0"

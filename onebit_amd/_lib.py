@@ -93,6 +93,10 @@ SYMBOLS = {
     "onebit_svid_route": (_int, [_i64, _i64, _int]),
     "onebit_svid_iterate": (_int, [_vp, _int, _i64, _vp, _vp, _vp, _vp, ctypes.c_size_t, _i64, _i64, _int, _vp]),   # (A, dtype, lda, w, h, stats, ws, ws_bytes, N, K, route, stream)
     "onebit_svid_emit": (_int, [_vp, _int, _i64, _vp, _vp, _vp, _int, _f, _vp, _vp, _vp, ctypes.c_size_t, _i64, _i64, _vp]),   # (A, dtype, lda, w, h, latent, latent_dtype, scale, packed, sums, ws, ws_bytes, N, K, stream)
+    # train-mode causal self-attention (additive to ABI 10)
+    "onebit_attention_train_forward": (_int, [_vp] * 5 + [_i64, _i64] + [ctypes.c_int32] * 3 + [_vp]),     # (q, k, v, o, lse, B, S, H, Hkv, D, stream)
+    "onebit_attention_train_workspace_bytes": (ctypes.c_size_t, [_i64, _i64] + [ctypes.c_int32] * 3),
+    "onebit_attention_train_backward": (_int, [_vp] * 10 + [ctypes.c_size_t, _i64, _i64] + [ctypes.c_int32] * 3 + [_vp]),   # (q, k, v, o, lse, dO, dq, dk, dv, ws, ws_bytes, B, S, H, Hkv, D, stream)
 }
 
 _lock = threading.Lock()

@@ -7,6 +7,7 @@ source or one of the headers it includes -- transitively -- is newer), linked in
   onebit_sample.hip  ABI 10: the sampler (temperature / top-k / top-p, Gumbel-max draw) that the *_sampled steps launch
   onebit_kd.hip      the knowledge-distillation loss (token KL + cross-entropy, hidden-state distance), forward and backward
   onebit_svid.hip    SVID start checkpoints: the rank-1 NMF of |W| (weight_scale, input_factor) and the sign / pack / residual pass
+  onebit_attn_train.hip  train-mode causal self-attention: forward with log-sum-exp, and the dq / dk / dv backward
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(CSRC, "libonebit_hip.so")
-SOURCES = ["onebit_hip.hip", "onebit_mixed.hip", "onebit_sample.hip", "onebit_kd.hip", "onebit_svid.hip"]
+SOURCES = ["onebit_hip.hip", "onebit_mixed.hip", "onebit_sample.hip", "onebit_kd.hip", "onebit_svid.hip", "onebit_attn_train.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-value"]
 
 
