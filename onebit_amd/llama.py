@@ -480,6 +480,18 @@ class OneBitLlamaForCausalLM(nn.Module):
         return torch.cat(out, dim=1)
 
 
+def _eos_set(eos_token_id) -> set:
+    return set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else {int(eos_token_id)}
+
+
+def _cut_at_eos(tokens: list, eos_token_id) -> list:
+    """``tokens`` up to and including the first EOS token (``eos_token_id``: int, list or None = no cut)."""
+    if eos_token_id is None:
+        return tokens
+    eos = _eos_set(eos_token_id)
+    return tokens[:next((j + 1 for j, t in enumerate(tokens) if t in eos), len(tokens))]
+
+
 def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_token_id=None, pad_token_id=None, do_sample: bool = False,
                      temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed=None, speculative=None) -> torch.Tensor:
     """``generate`` on the native engines, same return contract: B = 1 -> ``DecodeEngine`` (the prompt through ``onebit_mixed_step``,
@@ -502,13 +514,10 @@ def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_tok
                                   "(ContinuousBatcher) does not speculate")
     if max_new_tokens < 1:
         return input_ids
-    eos = None
-    if eos_token_id is not None:
-        eos = set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else {int(eos_token_id)}
-        if pad_token_id is None:
-            if B > 1:
-                raise ValueError("generate: eos_token_id with batch > 1 needs pad_token_id (generation/utils.py:2543)")
-            pad_token_id = next(iter(eos)) if not isinstance(eos_token_id, (list, tuple)) else int(eos_token_id[0])
+    if eos_token_id is not None and pad_token_id is None:
+        if B > 1:
+            raise ValueError("generate: eos_token_id with batch > 1 needs pad_token_id (generation/utils.py:2543)")
+        pad_token_id = int(eos_token_id[0]) if isinstance(eos_token_id, (list, tuple)) else next(iter(_eos_set(eos_token_id)))
     dev = self.lm_head.weight.device
     sp = None
     if do_sample:
@@ -543,10 +552,10 @@ def _generate_native(self, input_ids: torch.Tensor, max_new_tokens: int, eos_tok
         rows = [out[i] for i in ids]
         for i in ids:
             cb.sched.finished.pop(i, None)
-    if eos is not None:
-        ends = [next((j + 1 for j, t in enumerate(r) if t in eos), len(r)) for r in rows]
-        n = max(ends)
-        rows = [r[:e] + [pad_token_id] * (n - e) for r, e in zip(rows, ends)]
+    if eos_token_id is not None:
+        rows = [_cut_at_eos(r, eos_token_id) for r in rows]
+        n = max(len(r) for r in rows)
+        rows = [r + [pad_token_id] * (n - len(r)) for r in rows]
     new = torch.tensor(rows, dtype=input_ids.dtype, device=dev)
     return torch.cat([input_ids.to(dev), new], dim=1)
 

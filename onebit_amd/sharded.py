@@ -499,47 +499,34 @@ class _HipSegments:
     def __init__(self, dec: "FusedKShardedDecoder"):
         import ctypes
         from . import _lib
-        from .engine import _KState, _Model, _model_struct, fp16_view
+        from ._abi import _KState, _model_struct, make_state
+        from .engine import _call
         if not dec.dev.type == "cuda":
             raise RuntimeError("FusedKShardedDecoder needs the model on a ROCm GPU (no CPU fallback)")
-        self._ct, self._lib_mod = ctypes, _lib
+        self._ct, self._call = ctypes, _call
         self.lib = _lib.load()
         self.dec = dec
         self._model, self._keep = _model_struct(dec.model, dec.cache.layers, dec.max_len, krange=dec.kr)
-        b = dec.buf
-        self.lib.onebit_decode_stats_floats.restype = ctypes.c_size_t
-        self.lib.onebit_decode_stats_floats.argtypes = [ctypes.POINTER(_Model)]
+        cfg = dec.cfg
         self._tile_stats = torch.zeros(max(int(self.lib.onebit_decode_stats_floats(ctypes.byref(self._model))), 1),
                                        dtype=torch.float32, device=dec.dev)
-        p = lambda t: t.data_ptr()
-        self._state = _KState(ctypes.sizeof(_KState), p(dec.token), p(dec.pos), p(dec.out_tokens), dec.max_len,
-                              p(b["hres0"]), p(b["hres1"]), p(b["x"]), p(b["u_q"]), p(b["u_k"]), p(b["u_v"]), p(b["attn_out"]),
-                              p(b["u_gate"]), p(b["u_up"]), p(b["act"]), p(b["u_down"]),
-                              p(dec.z_qkv), p(dec.z_o), p(dec.z_gu), p(dec.z_down),
-                              p(b["logits"]), p(b["part_val"]), p(b["part_idx"]), p(self._tile_stats),
-                              dec.kr(dec.cfg.hidden_size)[0], dec.kr(dec.cfg.num_attention_heads * dec.cfg.head_dim)[0],
-                              dec.kr(dec.cfg.intermediate_size)[0], 0, 0, None)
+        ptrs = dict(dec.buf, token=dec.token, pos=dec.pos, out_tokens=dec.out_tokens, z_qkv=dec.z_qkv, z_o=dec.z_o, z_gu=dec.z_gu,
+                    z_down=dec.z_down, tile_stats=self._tile_stats)
+        ints = dict(max_out=dec.max_len, k0_hidden=dec.kr(cfg.hidden_size)[0], k0_attn=dec.kr(cfg.num_attention_heads * cfg.head_dim)[0],
+                    k0_inter=dec.kr(cfg.intermediate_size)[0])
         if dec.attn_chunk:
             # key-block attention: ONE graph serves every context, so the split count covers max_len (splits past a step's
             # context leave at once)
             splits = -(-dec.max_len // dec.attn_chunk)
             if splits > 64:
                 raise ValueError(f"attn_chunk {dec.attn_chunk} gives {splits} > 64 attention splits at max_len {dec.max_len}")
-            self.lib.onebit_attention_decode_scratch_bytes.restype = ctypes.c_size_t
-            nb = int(self.lib.onebit_attention_decode_scratch_bytes(1, dec.cfg.num_attention_heads, splits))
-            self._attn_scratch = torch.zeros(max(nb, 16), dtype=torch.uint8, device=dec.dev)
-            self._state.attn_chunk, self._state.attn_splits = dec.attn_chunk, splits
-            self._state.attn_scratch = self._attn_scratch.data_ptr()
-        self.lib.onebit_decode_step_ksharded.restype = ctypes.c_int
-        self.lib.onebit_decode_step_ksharded.argtypes = [ctypes.POINTER(_Model), ctypes.POINTER(_KState), ctypes.c_int32, ctypes.c_int32,
-                                                         ctypes.c_void_p]
+            nb = int(self.lib.onebit_attention_decode_scratch_bytes(1, cfg.num_attention_heads, splits))
+            self._attn_scratch = ptrs["attn_scratch"] = torch.zeros(max(nb, 16), dtype=torch.uint8, device=dec.dev)
+            ints.update(attn_chunk=dec.attn_chunk, attn_splits=splits)
+        self._state = make_state(_KState, ptrs, **ints)
 
     def segment(self, layer: int, seg: int):
-        dev = self.dec.dev
-        with torch.cuda.device(dev):
-            rc = self.lib.onebit_decode_step_ksharded(self._ct.byref(self._model), self._ct.byref(self._state), layer, seg,
-                                                      torch.cuda.current_stream(dev).cuda_stream)
-        self._lib_mod.check(rc, "onebit_decode_step_ksharded")
+        self._call(self.lib, self.dec.dev, "onebit_decode_step_ksharded", self._ct.byref(self._model), self._ct.byref(self._state), layer, seg)
 
 
 class FusedKShardedDecoder:

@@ -64,7 +64,6 @@ def test_argument_errors_without_gpu():
     layers = (_Layer * 1)()
     m = _Model(1, 64, 128, 2, 2, 32, 16, 8, 1e-6, 1e-5, layers, a, a, a, a, a)
     st = _BatchState(ctypes.sizeof(_BatchState), 1, a, a, a, a, a, a, a, a, a, a, a, a, a, a)
-    lib.onebit_decode_step_batched.argtypes = [ctypes.POINTER(_Model), ctypes.POINTER(_BatchState), ctypes.c_void_p]
     assert lib.onebit_decode_step_batched(ctypes.byref(m), ctypes.byref(st), None) == E_SHAPE      # batch 1
     assert b"batch" in lib.onebit_last_error()
     # ABI 8: a state built against another header (another size) is refused before any field is read
@@ -73,12 +72,10 @@ def test_argument_errors_without_gpu():
     assert b"struct_size" in lib.onebit_last_error()
     from onebit_amd.engine import _State
     ds = _State()
-    lib.onebit_decode_step.argtypes = [ctypes.POINTER(_Model), ctypes.POINTER(_State), ctypes.c_void_p]
     assert lib.onebit_decode_step(ctypes.byref(m), ctypes.byref(ds), None) == E_ARG                # struct_size 0
     assert b"struct_size" in lib.onebit_last_error()
     # the K-sharded decode step validates before any launch as well: null / foreign-size state, unknown segment, layer range
     from onebit_amd.engine import _KState
-    lib.onebit_decode_step_ksharded.argtypes = [ctypes.POINTER(_Model), ctypes.POINTER(_KState), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
     assert lib.onebit_decode_step_ksharded(None, None, 0, 0, None) == E_ARG
     ks = _KState()
     assert lib.onebit_decode_step_ksharded(ctypes.byref(m), ctypes.byref(ks), 0, 0, None) == E_ARG and b"struct_size" in lib.onebit_last_error()
@@ -125,8 +122,6 @@ def test_round6_entry_points_reject_bad_arguments_without_gpu():
     assert lib.onebit_linear_group_prescaled(ctypes.cast(pr, ctypes.c_void_p), up, up, 1, 500, None) == E_SHAPE
     assert lib.onebit_linear_group_prescaled(ctypes.cast(pr, ctypes.c_void_p), up, up, 2, 0, None) == 0
     # the mixed step: struct size, head_dim, row accounting, workspace
-    lib.onebit_mixed_step.argtypes = [ctypes.POINTER(_Model), ctypes.POINTER(_MixedState), ctypes.c_void_p]
-    lib.onebit_mixed_workspace_bytes.argtypes = [ctypes.POINTER(_Model), ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
     layers = (_Layer * 1)()
     m = _Model(1, 128, 352, 2, 2, 64, 96, 32, 1e-6, 1e-5, layers, a, a, a, a, a)
     assert lib.onebit_mixed_workspace_bytes(ctypes.byref(m), 0, 4, 0) == 0
@@ -176,3 +171,100 @@ def test_cpu_tensors_fail_loudly():
         m(torch.zeros(1, 64, dtype=torch.float16))
     with pytest.raises(RuntimeError):
         m(torch.zeros(1, 32, dtype=torch.float16))
+
+
+# ------------------------------------------------------------------------------------------- the struct mirrors and their filling --
+_MIRRORS = {"_Proj": "onebit_proj_t", "_Layer": "onebit_layer_t", "_Model": "onebit_model_t", "_State": "onebit_decode_state_t",
+            "_BatchState": "onebit_batch_state_t", "_KState": "onebit_kshard_state_t", "_Seg": "onebit_seg_t",
+            "_MixedState": "onebit_mixed_state_t", "_SpecState": "onebit_spec_state_t", "_FusedIn": "onebit_fused_in_t"}
+
+
+def _header_structs():
+    """typedef name -> [(base type, is pointer, array length or None, field name)] in declaration order."""
+    src = open(os.path.join(ROOT, "include", "onebit.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    out = {}
+    for body, name in re.findall(r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(onebit_\w+_t)\s*;", src, flags=re.S):
+        fields = []
+        for decl in body.split(";"):
+            decl = " ".join(decl.split())
+            if not decl:
+                continue
+            base, rest = re.fullmatch(r"((?:const )*\w+)\s*(.*)", decl).groups()
+            for d in rest.split(","):
+                fname, arr = re.search(r"(\w+)\s*(?:\[(\d+)\])?$", d.strip()).groups()
+                fields.append((base.replace("const ", ""), "*" in d, int(arr) if arr else None, fname))
+        out[name] = fields
+    return out
+
+
+def test_struct_mirrors_match_the_header_field_by_field():
+    """The library's struct_size check sees a mirror's total size only: two swapped pointers pass it.  Every mirror's _fields_ against
+    the header's declarations, in order: the name, and the type class (any pointer, the integer width and sign, float, a nested
+    onebit_proj_t, an array's length)."""
+    from onebit_amd import _abi
+    scalar = {"int32_t": ctypes.c_int32, "int": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+              "size_t": ctypes.c_size_t, "float": ctypes.c_float, "onebit_proj_t": _abi._Proj}
+    is_ptr = lambda t: t is ctypes.c_void_p or issubclass(t, ctypes._Pointer)
+    structs = _header_structs()
+    assert len(_MIRRORS) == 10
+    for mirror, typedef in _MIRRORS.items():
+        got, want = getattr(_abi, mirror)._fields_, structs[typedef]
+        assert [f[0] for f in got] == [w[3] for w in want], (mirror, typedef)
+        for (fname, ftype), (base, ptr, arr, _) in zip(got, want):
+            if arr is not None:
+                assert issubclass(ftype, ctypes.Array) and ftype._length_ == arr, (mirror, fname)
+                ftype = ftype._type_
+            assert is_ptr(ftype) if ptr else ftype is scalar[base], (mirror, fname, base)
+    # the parser itself: comma lists, pointers that bind to the declarator, an array of pointers
+    assert structs["onebit_seg_t"] == [("int32_t", False, None, n) for n in ("row0", "n", "slot", "past")]
+    assert structs["onebit_layer_t"][:2] == [("onebit_proj_t", False, None, "q"), ("onebit_proj_t", False, None, "k")]
+    assert structs["onebit_layer_t"][9:11] == [("void", True, None, "k_cache"), ("void", True, None, "v_cache")]
+    assert structs["onebit_fused_in_t"][-1] == ("float", True, 3, "st_out")
+
+
+def test_make_state_fills_by_name_and_rejects_unknown_fields():
+    from onebit_amd._abi import _Seg, _State, make_state
+    t = torch.zeros(4)
+    st = make_state(_State, dict(u_q=t, u_k=None), max_out=7)
+    assert st.struct_size == ctypes.sizeof(_State) and st.u_q == t.data_ptr() and st.u_k is None and st.max_out == 7 and st.u_v is None
+    with pytest.raises(AttributeError):
+        make_state(_State, dict(u_qq=t))
+    with pytest.raises(AttributeError):
+        make_state(_State, attn_blnd=64)
+    cp = make_state(st, dict(u_k=t), attn_blind=64)                 # a copy of an instance: the original is left alone
+    assert cp.u_q == st.u_q and cp.u_k == t.data_ptr() and cp.attn_blind == 64 and cp.max_out == 7
+    assert st.u_k is None and st.attn_blind == 0
+    with pytest.raises(AttributeError):
+        make_state(st, u_qq=1)
+    sg = make_state(_Seg, row0=1, n=2, slot=3, past=4)              # no struct_size field: nothing invented
+    assert (sg.row0, sg.n, sg.slot, sg.past) == (1, 2, 3, 4) and not hasattr(sg, "struct_size")
+
+
+def test_step_variant_table():
+    """Which form of onebit_decode_step serves a step, by the number of cached tokens (today's rule worked by hand)."""
+    from onebit_amd.engine import step_variant
+    kw = dict(long_from=160, short_ok=True, keyblock=True, kb_chunk=128, kb_top=4)
+    want = {0: "64", 63: "64", 64: "short", 159: "short", 160: ("kb", 2), 255: ("kb", 2), 256: ("kb", 4), 511: ("kb", 4)}
+    for steps, key in want.items():
+        assert step_variant(steps, **kw) == key, steps
+    assert step_variant(160, **dict(kw, keyblock=False)) == "long"
+    assert step_variant(0, **dict(kw, long_from=1, short_ok=False)) == ("kb", 1)
+    assert step_variant(400, **dict(kw, long_from=0)) == "short"
+
+
+def test_library_functions_are_typed_once():
+    """_lib.SYMBOLS is the only typing of the library's functions (an argtypes assignment elsewhere would change a process-global
+    function object under every other caller).  Last in this file: the tests above have made their calls."""
+    assign = re.compile(r"\.(argtypes|restype)\s*=")
+    files = [os.path.join(d, f) for d in (os.path.join(ROOT, "onebit_amd"), os.path.join(ROOT, "tests"))
+             for f in sorted(os.listdir(d)) if f.endswith(".py") and not (d.endswith("onebit_amd") and f == "_lib.py")]
+    assert len(files) > 20
+    for path in files:
+        hits = [i + 1 for i, line in enumerate(open(path)) if assign.search(line)]
+        assert not hits, (path, hits)
+    lib = _lib.load()
+    for name, (res, args) in _lib.SYMBOLS.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name

@@ -223,9 +223,10 @@ def test_engine_attention_variants(cfgkw, prompt_len, steps, engine_kw):
         tok = lg[:, -1].argmax(-1, keepdim=True)
         ref_toks.append(int(tok))
     eng = DecodeEngine(model, max_len=cfg.max_position_embeddings, **engine_kw)
-    assert (eng.graph_long is not None or bool(eng._kb_graphs)) == bool(engine_kw.get("long_context_from"))
-    assert bool(eng._kb_graphs) == (bool(engine_kw.get("long_context_from")) and engine_kw.get("long_attention") == "keyblock")
-    assert eng.graph64 is not None and eng._state64.attn_blind == 64 and eng._state.attn_blind == 0
+    kb_graphs = [k for k, sampled in eng._graphs if isinstance(k, tuple) and not sampled]
+    assert (("long", False) in eng._graphs or bool(kb_graphs)) == bool(engine_kw.get("long_context_from"))
+    assert bool(kb_graphs) == (bool(engine_kw.get("long_context_from")) and engine_kw.get("long_attention") == "keyblock")
+    assert ("64", False) in eng._graphs and eng._variants["64"].attn_blind == 64 and eng._variants["short"].attn_blind == 0
     eng.prefill(ids)
     assert eng.first_token == ref_toks[0]
     ref = np.stack(ref_logits)
@@ -257,6 +258,33 @@ def test_engine_is_deterministic_across_graphs_and_runs():
         kb.append(eng.generate(ids, 200)[0].tolist())
     assert kb[0] == kb[1]
     assert len(set(runs[0][40:])) > 8            # not a degenerate constant stream
+
+
+def test_engine_graphs_equal_direct_launches_across_every_variant():
+    """300 tokens from a 4-token prompt with max_len 320, long_context_from 160 and 64-position key blocks: the steps pass position
+    64 ("64" -> "short"), position 160 (-> key-block attention) and split counts up to 8.  Replayed graphs and direct launches give
+    the same tokens, greedy and sampled, and construction captures exactly one greedy graph per variant it built."""
+    from onebit_amd.engine import DecodeEngine
+    from onebit_amd.llama import OneBitLlamaConfig, build_synthetic_model
+    from onebit_amd.sampling import SamplingParams
+    dev = torch.device("cuda:0")
+    cfg = OneBitLlamaConfig(vocab_size=1000, hidden_size=128, intermediate_size=352, num_hidden_layers=2, num_attention_heads=2,
+                            max_position_embeddings=320)
+    model = build_synthetic_model(cfg, seed=21, device=dev)
+    ids = torch.randint(0, cfg.vocab_size, (1, 4), generator=torch.Generator().manual_seed(8)).to(dev)
+    sp = SamplingParams(0.9, 50, 0.9, seed=31, stream=1)
+    out = {}
+    for use_graph in (True, False):
+        eng = DecodeEngine(model, max_len=320, long_context_from=160, attn_chunk=64, use_graph=use_graph)
+        greedy_keys = {k for k, sampled in eng._graphs if not sampled}
+        assert greedy_keys == ({"short", "64", ("kb", 1), ("kb", 2), ("kb", 4), ("kb", 8)} if use_graph else set())
+        out[use_graph] = (eng.generate(ids, 300)[0].tolist(), eng.generate(ids, 300, sampling=sp)[0].tolist())
+        sampled_keys = {k for k, sampled in eng._graphs if sampled}
+        assert sampled_keys == ({"short", "64", ("kb", 4), ("kb", 8)} if use_graph else set())      # captured on first use only
+        assert {k for k, sampled in eng._graphs if not sampled} == greedy_keys
+    assert len(out[True][0]) == 304 and len(set(out[True][0][4:])) > 8          # not a degenerate constant stream
+    assert out[True][0] == out[False][0]
+    assert out[True][1] == out[False][1] and out[True][1] != out[True][0]
 
 
 def test_fused_gemv_propagates_non_finite_activations():
@@ -516,15 +544,15 @@ def test_attn_blind_hint_does_not_change_results():
         outs = []
         for b64 in (False, True):
             eng.set_state(7, pos)
-            eng._launch(blind64=b64)
+            eng._launch("64" if b64 else "short")
             torch.cuda.synchronize()
             outs.append(eng.buf["logits"].clone())
         assert torch.equal(outs[0], outs[1]), pos
-    eng._state64.attn_blind = 32
+    eng._variants["64"].attn_blind = 32
     eng.set_state(7, 5)
     with pytest.raises(Exception, match="attn_blind"):
-        eng._launch(blind64=True)
-    eng._state64.attn_blind = 64
+        eng._launch("64")
+    eng._variants["64"].attn_blind = 64
 
 
 @pytest.mark.parametrize("cfgkw,S,rows", [

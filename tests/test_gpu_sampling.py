@@ -154,8 +154,8 @@ def test_decode_step_sampled_matches_standalone_kernel():
     for i, sp in enumerate([SamplingParams(0.8, 50, 0.9, seed=5), None, SamplingParams(1.2, 0, 1.0, seed=9, stream=3)] * 4):
         pr = pack([sp], DEV)
         p = int(eng.pos.item())
-        st = eng._state64 if p < 64 else eng._state
-        rc = lib.onebit_decode_step_sampled(ctypes.addressof(eng._model), ctypes.addressof(st), pr.data_ptr(),
+        st = eng._variants["64" if p < 64 else "short"]
+        rc = lib.onebit_decode_step_sampled(ctypes.byref(eng._model), ctypes.byref(st), pr.data_ptr(),
                                             torch.cuda.current_stream(DEV).cuda_stream)
         _lib.check(rc, "onebit_decode_step_sampled")
         torch.cuda.synchronize()
@@ -248,7 +248,8 @@ def test_decode_engine_sampled_graphs_match_standalone_kernel():
         t = int(eng.token.item())
         assert t == int(sample_logits(eng.buf["logits"][None], pr, [p + 1]).item()), p
         toks.append(t)
-    assert {"64", "short"} <= set(eng._sgraphs) and any(isinstance(k, tuple) for k in eng._sgraphs)
+    sampled = {k for k, s in eng._graphs if s}
+    assert {"64", "short"} <= sampled and any(isinstance(k, tuple) for k in sampled)
     assert eng.generate(ids, len(toks), sampling=sp)[0, 30:].tolist() == toks
     g = eng.generate(ids, 40)[0, 30:].tolist()                       # greedy again afterwards: the greedy graphs
     assert g == eng.generate(ids, 40)[0, 30:].tolist() and eng._sampled is False

@@ -43,7 +43,7 @@ def _commit(lib, L, chosen, drafts, pos, remaining, history, max_len, nmax, nmin
     d_pos, d_rem, d_rec = ti([pos]), ti([remaining]), torch.full((3,), -9, dtype=torch.int32, device=dev)
     st = _SpecState(ctypes.sizeof(_SpecState), k, 1, 64, 1, nmax, nmin, d_tok.data_ptr(), None, d_rp.data_ptr(), d_dr.data_ptr(), d_ch.data_ptr(),
                     d_pos.data_ptr(), d_rem.data_ptr(), hist.data_ptr(), d_rec.data_ptr(), None, None, None, None, 0)
-    L.check(lib.onebit_spec_commit(ctypes.addressof(st), max_len, _sp()), "spec_commit")
+    L.check(lib.onebit_spec_commit(ctypes.byref(st), max_len, _sp()), "spec_commit")
     torch.cuda.synchronize()
     rec = d_rec.tolist()
     return dict(n_acc=rec[0], pos=int(d_pos[0]), rec_pos=rec[1], n_drafted=rec[2], remaining=int(d_rem[0]), history=hist.tolist(),

@@ -87,7 +87,6 @@ def test_spec_entry_points_exported_and_reject_bad_arguments_without_gpu():
     a = (ctypes.addressof(buf) + 255) & ~255
     layers = (_Layer * 1)()
     m = _Model(1, 64, 128, 1, 1, 64, 16, 32, 1e-6, 1e-5, layers, a, a, a, a, a)
-    lib.onebit_spec_workspace_bytes.argtypes = [ctypes.POINTER(_Model), ctypes.c_int32, ctypes.c_int32]
     assert lib.onebit_spec_workspace_bytes(ctypes.byref(m), 0, 64) == 0 and lib.onebit_spec_workspace_bytes(ctypes.byref(m), 16, 64) == 0
     need = lib.onebit_spec_workspace_bytes(ctypes.byref(m), 4, 64)
     assert need > 0 and lib.onebit_spec_workspace_bytes(ctypes.byref(m), 8, 64) > need
@@ -101,7 +100,7 @@ def test_spec_entry_points_exported_and_reject_bad_arguments_without_gpu():
 
     def step(**kw):
         st = state(**kw)                                        # (kept alive across the call)
-        return lib.onebit_spec_step(ctypes.addressof(m), ctypes.addressof(st), None)
+        return lib.onebit_spec_step(ctypes.byref(m), ctypes.byref(st), None)
 
     assert lib.onebit_spec_step(None, None, None) == E_ARG
     assert step(k=0) == E_ARG and b"draft" in lib.onebit_last_error()
@@ -114,7 +113,7 @@ def test_spec_entry_points_exported_and_reject_bad_arguments_without_gpu():
     assert step(nb=need - 1) == E_WSPACE
     def prm(**kw):
         st = state(**kw)
-        return lib.onebit_spec_step_sampled(ctypes.addressof(m), ctypes.addressof(st), kw.get("params", a), None)
+        return lib.onebit_spec_step_sampled(ctypes.byref(m), ctypes.byref(st), kw.get("params", a), None)
 
     assert prm(params=None) == E_ARG and prm() == E_ARG and b"logits" in lib.onebit_last_error()
     assert prm(k=16, logits=a) == E_ARG
@@ -126,7 +125,7 @@ def test_spec_entry_points_exported_and_reject_bad_arguments_without_gpu():
     assert mq(pos=None) == E_ARG and mq(rows=0) == 0
     assert lib.onebit_spec_commit(None, 64, None) == E_ARG
     st = state()
-    assert lib.onebit_spec_commit(ctypes.addressof(st), 20000, None) == E_SHAPE
+    assert lib.onebit_spec_commit(ctypes.byref(st), 20000, None) == E_SHAPE
 
 
 def test_generate_native_refuses_speculative_batches():

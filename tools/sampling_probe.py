@@ -57,7 +57,7 @@ def main():
         kernel_only()
         return
     import bench
-    from onebit_amd.engine import BatchedDecodeStep, DecodeEngine, fp16_view
+    from onebit_amd.engine import BatchedDecodeStep, DecodeEngine, fp16_view, step_variant
     from onebit_amd.llama import build_synthetic_model
     cfg = bench.model_config("7b")
     model = build_synthetic_model(cfg, seed=4242, device=dev)
@@ -68,8 +68,8 @@ def main():
     eng.prime(ids)
     print("7B synthetic, top_k 50 / top_p 0.9 / temperature 0.8")
     for ctx in (128, 1900):
-        long = ctx >= eng._long_from > 0
-        st = eng._kb_states[eng._kb_splits(ctx + 65)][0] if long and eng._keyblock else (eng._state_long if long else eng._state)
+        key = step_variant(ctx, eng._long_from, eng._short_ok, eng._keyblock, eng._kb_chunk, eng._kb_top)
+        st = eng._variants["short" if key == "64" else key]
         stream = lambda: torch.cuda.current_stream(dev).cuda_stream
 
         def greedy():
@@ -78,7 +78,7 @@ def main():
 
         def sampled():
             eng.pos.fill_(ctx)
-            _lib.check(lib.onebit_decode_step_sampled(ctypes.addressof(eng._model), ctypes.addressof(st), pr1.data_ptr(), stream()), "decode_sampled")
+            _lib.check(lib.onebit_decode_step_sampled(ctypes.byref(eng._model), ctypes.byref(st), pr1.data_ptr(), stream()), "decode_sampled")
         a, b = ab(greedy, sampled)
         print(f"decode step at {ctx} cached tokens: greedy {a:.4f} ms/token, sampled {b:.4f} ms/token ({b / a:.3f}x)", flush=True)
     del eng
